@@ -27,6 +27,11 @@ that a lossless packing win is never read as bandwidth; `roofline_learner` for k
 `cpu_baseline` times the CPU oracle port on the host cores (1 core and all cores); `other_configs` (N = 1, default
 command only) carries BASELINE.json configs[2..4] and the env-only 65 536 / 262 144-agent points, each run as a child
 process of this one for >= 0.5 s of timed region.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step -- the transition it wrote into
+the ring, the observation it left for the next pass, the weights and the loss -- as DIR/<name>.npy (f32; at most 64 MB, a fixed
+seeded sample of rows for larger env batches).  The inputs are seeded, so two builds run with the same arguments compare output
+for output.
 """
 from __future__ import annotations
 
@@ -338,6 +343,8 @@ def parse():
                    help="skip the 1 024 extra policy + step launches that count episode ends (scripts/profile_round.sh: under rocprofv3 "
                         "they would enter the kernel's average -- each follows a torch reduction, not a learner launch)")
     p.add_argument("--full-line", action="store_true", help="print the whole result dict instead of the bounded headline line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the timed path computed in its last step to DIR/<name>.npy (rank 0)")
     p.add_argument("--no-obs", action="store_true", help="diagnostic (env-only): skip the observation")
     p.add_argument("--env-only", action="store_true", help="diagnostic: time only back-to-back k_step launches")
     p.add_argument("--bank", default="gpu", choices=["gpu", "packaged"],
@@ -661,6 +668,10 @@ def run_config4(args, dev, world_size=1, rank=0):
         run_passes(pps)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(ring_outputs(env, ring), action1=a1_plane[(ring.head - 1) % ring.frames]),
+                     {"slot%d_params" % j: net_params(L.actor, L.critic_1, L.critic_2, L.target_critic_1, L.target_critic_2)
+                      for j, L in enumerate(learners)})
     ident = None
     if multi:
         got = [None] * world_size
@@ -762,6 +773,43 @@ def run_config4(args, dev, world_size=1, rank=0):
     return out
 
 
+# ---- --dump-outputs --------------------------------------------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_ROWS = 32768                  # per-agent arrays longer than this keep a fixed, seeded sample of their rows
+
+
+def net_params(*nets) -> torch.Tensor:
+    """The parameters of `nets`, flattened and concatenated in module order."""
+    return torch.cat([p.detach().reshape(-1).float() for net in nets for p in net.parameters()])
+
+
+def ring_outputs(env, ring) -> dict:
+    """The transition the last pass wrote into the ring (frame head - 1) and the observation it left at head, unpacked to f32."""
+    t = (ring.head - 1) % ring.frames
+    return {"action": ring.action[t], "reward": ring.reward[t], "done": ring.done[t], "valid": ring.valid[t],
+            "next_obs": env.unpack(ring.obs[ring.head])}
+
+
+def dump_outputs(path: str, per_agent: dict, whole: dict = None) -> None:
+    """Write the arrays (device tensors) as path/<name>.npy, f32 (f64 stays f64).  `per_agent` arrays (first dimension = agents)
+    longer than DUMP_MAX_ROWS keep the rows of one fixed, seeded sample, whose indices go to path/sample_rows.npy, so that two
+    builds compare row for row; `whole` arrays (weights, loss) are written as they are."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: v.detach().cpu().numpy() for k, v in per_agent.items()}
+    n = {v.shape[0] for v in out.values()}
+    assert len(n) <= 1, "per-agent arrays of different lengths: %s" % sorted(n)
+    if n and next(iter(n)) > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(next(iter(n)), DUMP_MAX_ROWS, replace=False))
+        out = {k: v[rows] for k, v in out.items()}
+        out["sample_rows"] = rows
+    out.update({k: v.detach().cpu().numpy() for k, v in (whole or {}).items()})
+    out = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype in (np.float64, np.int64) else np.float32) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes > %d" % (total, DUMP_MAX_BYTES)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def spawn_ranks(args) -> int:
     """`python bench.py --gpus N` with no rank environment: start the N ranks here -- this file re-executed under
     torch.distributed.run, one process per GPU of this node, rendezvous on 127.0.0.1 -- and pass rank 0's line through."""
@@ -770,7 +818,8 @@ def spawn_ranks(args) -> int:
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
-    n_dev = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    # (with --same-device this process never touches the GPU: only the ranks hold it open)
+    n_dev = 0 if args.same_device else (torch.cuda.device_count() if torch.cuda.is_available() else 0)
     if not args.same_device and n_dev < args.gpus:
         raise SystemExit("--gpus %d asked for, %d visible (test several ranks on one GPU with --same-device --dist-backend gloo)"
                          % (args.gpus, n_dev))
@@ -926,6 +975,8 @@ def run_dqn(args, world_size, rank, dev):
         e1.record()
         torch.cuda.synchronize(dev)
         ms = e0.elapsed_time(e1) / iters
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, ring_outputs(env, ring))
         algo = 404 if args.obs_dtype == "f16" else ALGO_BYTES_PER_AGENT_STEP
         gbs = algo * env.N / (ms * 1e-3) / 1e9
         model = step_bytes_model(ring.obs.shape[-1] * ring.obs.element_size(), env.N, policy=False, records=False)
@@ -1113,6 +1164,9 @@ def run_dqn(args, world_size, rank, dev):
     dt = max_over_ranks(dt)
     n_pass = args.steps * pps
     hot, use_c = state["hot"], state["use_c"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ring_outputs(env, ring),
+                     {"q_local": net_params(learner.q_local), "q_target": net_params(learner.q_target), "loss": learner.loss.reshape(1)})
 
     # ---- N > 1: are the ranks still bit-identical?  (they must be under any per-update exchange of the gradient sums)
     multi_report = {}

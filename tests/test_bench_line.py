@@ -76,3 +76,51 @@ def test_step_bytes_model_adds_up_to_what_the_counters_saw():
     for key, n in (("envonly65536_packed", 65536), ("envonly262144_packed", 262144)):
         e = bench.step_bytes_model(80, n, policy=False, records=False)
         assert summ[key]["k_step_traffic_bytes_per_launch"] / n == pytest.approx(e["total"], rel=0.10), key
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_long_ones(tmp_path):
+    """bench.dump_outputs (--dump-outputs): every array as <name>.npy in f32 (f64 kept), the rows of per-agent arrays longer than
+    DUMP_MAX_ROWS reduced to one fixed sample whose indices are written too, the same sample on every call; weights whole."""
+    import numpy as np
+    import torch
+    n = bench.DUMP_MAX_ROWS + 1000
+    per_agent = {"action": torch.arange(n, dtype=torch.int32), "done": (torch.arange(n) % 3 == 0).to(torch.uint8),
+                 "next_obs": torch.arange(n * 4, dtype=torch.float32).reshape(n, 4)}
+    whole = {"w": torch.linspace(0, 1, 2 * n, dtype=torch.float64), "loss": torch.tensor([2.5])}
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), per_agent, whole)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"action", "done", "next_obs", "w", "loss", "sample_rows"}
+    rows = got["sample_rows"].astype(np.int64)
+    assert len(rows) == bench.DUMP_MAX_ROWS and np.all(np.diff(rows) > 0) and rows[-1] < n
+    assert got["action"].dtype == np.float32 and np.array_equal(got["action"], rows.astype(np.float32))
+    assert np.array_equal(got["done"], (rows % 3 == 0).astype(np.float32))
+    assert np.array_equal(got["next_obs"][:, 0], (rows * 4).astype(np.float32))
+    assert got["w"].dtype == np.float64 and np.array_equal(got["w"], whole["w"].numpy()) and got["loss"].tolist() == [2.5]
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    bench.dump_outputs(str(tmp_path / "c"), {"r": torch.ones(100)})
+    assert os.listdir(tmp_path / "c") == ["r.npy"]                         # short enough: every row, no sample
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "d"), {"big": torch.zeros((bench.DUMP_MAX_ROWS, 1024), dtype=torch.float32)})
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_its_last_step_computed(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's transition, next observation, weights and loss, all finite, the line's
+    `steps` as asked."""
+    import subprocess
+    import sys
+    import numpy as np
+    d = tmp_path / "out"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                          "--no-other-configs", "--full-line", "--envs", "2048", "--batch", "2048", "--replay", "16384",
+                          "--env-only-iters", "5", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert set(got) == {"action", "reward", "done", "valid", "next_obs", "q_local", "q_target", "loss"}
+    assert got["next_obs"].shape == (2048, 100) and got["reward"].shape == (2048,)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+    assert set(np.unique(got["action"])) <= {0.0, 1.0, 2.0} and len(got["q_local"]) == 100 * 64 + 64 + 3 * 64 + 3

@@ -1,7 +1,8 @@
 """The reflection-level drop-in boundary: reference-named plugin modules, XML config
 contract, factories, episode-loop ordering and result dict.  Host logic only: the vectorised env is the
 oracle-backed fake from tests/fake_backend.py (the GPU run of the same plugins is in test_plugins_gpu.py).
-When /root/reference is present the UNMODIFIED reference simulator.py drives our PathPlan_City plugin."""
+When build() has byte-compiled the reference into oracle/_ref/ (oracle/build_ref.py), the UNMODIFIED reference simulator drives
+our PathPlan_City plugin."""
 import os
 import random
 import sys
@@ -204,17 +205,20 @@ def test_run_eposide_with_sac_continuous_actions(cfg_dir):
     assert tr.epoch > 150 and np.isfinite(float(res["loss"]))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference checkout")
+REF_BUILD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
+
+
+@pytest.mark.skipif(not os.path.isfile(os.path.join(REF_BUILD, "simulator.pyc")),
+                    reason="needs the reference build in oracle/_ref (build() makes it where the reference checkout exists)")
 def test_unmodified_reference_simulator_drives_our_plugins(cfg_dir, monkeypatch):
-    """Drop-in proof: the reference's own simulator.py + factories (scratch copy), our plugin dir first on
-    sys.path, our PathPlan_City / UAV / building / DuelingDQN_Trainer behind its reflection."""
+    """Drop-in proof: the reference's own simulator + factories (a scratch copy of its byte-compiled modules, oracle/build_ref.py),
+    our plugin dir first on sys.path, our PathPlan_City / UAV / building / DuelingDQN_Trainer behind its reflection."""
     import shutil
     from oracle import ref_harness
     ref = cfg_dir / "ref"
-    shutil.copytree("/root/reference", ref, ignore=shutil.ignore_patterns("*.gif", "*.jpg", "doc", "Mod", "Envs", "Agents",
-                                                                          "Obstacles", "Trainer"))
+    shutil.copytree(REF_BUILD, ref)
     os.makedirs(ref / "logs", exist_ok=True)
-    driver.make_config_dir(str(ref), "DuelingDQN", num_envs=8, num_episodes=10)   # overwrites ref/config/*.xml
+    driver.make_config_dir(str(ref), "DuelingDQN", num_envs=8, num_episodes=10)   # writes ref/config/*.xml
     monkeypatch.chdir(ref)
     ref_harness.install_shims()
     for m in [m for m in sys.modules if m in ("simulator", "PathPlan_City", "UAV", "building", "CalMod") or
