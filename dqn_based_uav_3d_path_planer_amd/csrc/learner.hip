@@ -909,7 +909,9 @@ __device__ __forceinline__ void grad_products_split8b(const GradLdsP &L, const f
 }
 
 // SPLIT (round 5): the weight-gradient products in the split form -- see grad_products_split8 below.
-template <bool FIRST, int SPLIT>
+// GLDS (needs g.img): both layer-1 images come in by LDS-DMA (img_glds) -- the same bytes without the 28 staging registers per thread
+// and the ds_write pass; the staging barrier waits for them.
+template <bool FIRST, int SPLIT, bool GLDS>
 __device__ __forceinline__ void grad_tile_packed8(const GradArgs &g, const GradLdsP &L, float *qn_lds, int tile, bool more,
                                                   GradAcc8 &A)
 {
@@ -925,9 +927,11 @@ __device__ __forceinline__ void grad_tile_packed8(const GradArgs &g, const GradL
     SplitScRegs vS;
     float pw[4] = {0, 0, 0, 0}, pb2 = 0.0f;
     if (FIRST) {                              // group 0 stages q_local's weights, group 1 q_target's
-        if (g.img) img_issue(vW, g.img + (grp == 0 ? 0 : kSplitF)); else w_issue_half(vW, net, t256);
+        if (GLDS) img_glds(grp == 0 ? L.W1l : L.W1t, g.img + (grp == 0 ? 0 : kSplitF), strip);
+        else if (g.img) img_issue(vW, g.img + (grp == 0 ? 0 : kSplitF));
+        else w_issue_half(vW, net, t256);
         const NetDev nv = net_view(net, n2);
-        if (!g.img) w_issue_sc(vS, net, nv.b1);
+        if (!GLDS && !g.img) w_issue_sc(vS, net, nv.b1);
 #pragma unroll
         for (int k = 0; k < 4; ++k) pw[k] = nv.W2[t256 + 256 * k < n2 * kHid ? t256 + 256 * k : 0];
         pb2 = nv.b2[t256 < n2 ? t256 : 0];
@@ -961,8 +965,10 @@ __device__ __forceinline__ void grad_tile_packed8(const GradArgs &g, const GradL
     }
     L_STAMP(6);                               // (diagnostics: every load of the tile issued)
     if (FIRST) {
-        if (g.img) img_commit(grp == 0 ? L.W1l : L.W1t, vW); else w_commit_split(w1split_at(grp == 0 ? L.W1l : L.W1t), vW, vS);
-        L_STAMP(7);                           // (diagnostics: layer 1 committed -- its loads have arrived)
+        if (!GLDS) {
+            if (g.img) img_commit(grp == 0 ? L.W1l : L.W1t, vW); else w_commit_split(w1split_at(grp == 0 ? L.W1l : L.W1t), vW, vS);
+        }
+        L_STAMP(7);                           // (diagnostics: layer 1 committed -- its loads have arrived; GLDS: still in flight)
         float *W2 = grp == 0 ? L.W2l : L.W2t, *b2 = grp == 0 ? L.b2l : L.b2t;
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -1081,7 +1087,7 @@ __device__ __forceinline__ void grad_tile_packed8(const GradArgs &g, const GradL
     if (more) __syncthreads();                        // the next tile overwrites Ps / Hs / dHs / douts / qn
 }
 
-template <int SPLIT>
+template <int SPLIT, bool GLDS = false>
 __global__ void __launch_bounds__(512) k_dqn_grad_packed8(Grad2Args ga)
 {
     UAV_HOT_PRIO();
@@ -1112,9 +1118,9 @@ __global__ void __launch_bounds__(512) k_dqn_grad_packed8(Grad2Args ga)
     L_STAMP(0);
     const int step = (int)gridDim.x;
     int tile = (int)blockIdx.x;
-    grad_tile_packed8<true, SPLIT>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
+    grad_tile_packed8<true, SPLIT, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
     for (tile += step; tile < ga.n_tiles; tile += step)
-        grad_tile_packed8<false, SPLIT>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
+        grad_tile_packed8<false, SPLIT, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
     L_STAMP(5);
     // ---- the partial-gradient row of this workgroup: dW1 | db1 | dW2 | db2 | loss sum | valid count
     float *out = g.partials + (size_t)blockIdx.x * ga.stride;
@@ -2385,10 +2391,14 @@ int uavenv_dqn_grad_img(const UavReplayRing *ring, int32_t head, int32_t filled,
             // form B of the split products (group 1 all six flag tiles, their operands built while group 0 is in td_backward) is the
             // default: 11.48 -> 10.75 us per launch, 28.76 -> 28.2 us per configs[1] pass; UAVENV_DW1_SPLITA=1 selects form A
             static const bool dw1_b = getenv("UAVENV_DW1_SPLITA") == nullptr;
+            // (with a layer-1 image: form B stages both images by LDS-DMA; UAVENV_STAGE_VGPR=1 keeps the register-staged form -- A/B knob)
+            static const bool stage_vgpr = getenv("UAVENV_STAGE_VGPR") && atoi(getenv("UAVENV_STAGE_VGPR")) != 0;
             if (!attr8) {
                 if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed8<1>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess ||
                     hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed8<2>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess ||
+                    hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed8<2, true>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess ||
                     hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed8<0>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess)
@@ -2396,6 +2406,7 @@ int uavenv_dqn_grad_img(const UavReplayRing *ring, int32_t head, int32_t filled,
                 attr8 = true;
             }
             if (dw1_f32) hipLaunchKernelGGL(k_dqn_grad_packed8<0>, dim3(grid), dim3(512), kGradP8Lds, s, ga);
+            else if (dw1_b && g.img && !stage_vgpr) hipLaunchKernelGGL((k_dqn_grad_packed8<2, true>), dim3(grid), dim3(512), kGradP8Lds, s, ga);
             else if (dw1_b) hipLaunchKernelGGL(k_dqn_grad_packed8<2>, dim3(grid), dim3(512), kGradP8Lds, s, ga);
             else hipLaunchKernelGGL(k_dqn_grad_packed8<1>, dim3(grid), dim3(512), kGradP8Lds, s, ga);
             rc = UAVENV_OK;

@@ -413,6 +413,30 @@ __device__ __forceinline__ void img_commit(float *lds_image, const floatx4 (&v)[
         if (c < kImgPieces) *reinterpret_cast<floatx4 *>(lds_image + 4 * c) = v[it];
     }
 }
+// 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4): no VGPR destination, no ds_write.  The LDS
+// destination is NOT per lane: lane l of the wavefront writes lds_base + 16 l, so `lds_base` must be wavefront-uniform.  The copy is
+// counted on vmcnt; a __syncthreads() behind it waits for it (its fence emits vmcnt(0)).
+__device__ __forceinline__ void glds16(const void *src, void *lds_base)
+{
+    __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)src,
+                                     (__attribute__((address_space(3))) void *)lds_base, 16, 0, 0);
+}
+// The image by LDS-DMA: the same bytes as img_issue + img_commit, without the 28 staging registers per thread and the ds_write pass.
+// `w` = the calling wavefront's index 0..3 in its 256-thread team (wavefront-uniform); wavefront w, instruction it copies the
+// 64 pieces [(4 it + w) 64, +64): 27 KiB-instructions, seven for wavefronts 0..2, six for wavefront 3.
+constexpr int kImgDma = kImgPieces / 64;
+static_assert(kImgPieces % 64 == 0 && (kImgDma + 3) / 4 == 7 && kImgDma > 4 * 6, "the image is 27 whole wavefront-instructions");
+__device__ __forceinline__ void img_glds(float *lds_image, const float *img, int w)
+{
+    const int lane = (int)threadIdx.x & 63;
+#pragma unroll
+    for (int it = 0; it < 6; ++it) {
+        const int c = (4 * it + w) * 64;
+        glds16(img + 4 * (c + lane), lds_image + 4 * c);
+    }
+    const int c = (24 + w) * 64;
+    if (c < kImgPieces) glds16(img + 4 * (c + lane), lds_image + 4 * c);
+}
 // parameter p of a flat block (fc1 [64][100] | b1 [64] | ...) = w into an image in memory (the Adam kernels: one thread per parameter)
 __device__ __forceinline__ void img_store_param(float *img, int p, float w)
 {

@@ -220,6 +220,21 @@ __device__ __forceinline__ void stage_copy(unsigned char *smem, const StepArgs &
     }
 }
 
+// the same copy by LDS-DMA from `nw` wavefronts (this one is number `w`, wavefront-uniform): wavefront w, instruction j writes the
+// 64 pieces [(nw j + w) 64, +64); the lanes of a last partial instruction past the end are masked off (the LDS destination is
+// lane-linear, so they cannot be clamped onto the last piece as above).  Same bytes in LDS, no staging registers.
+__device__ __forceinline__ void stage_copy_glds(unsigned char *smem, const StepArgs &a, int w, int nw)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const uint4 *src = reinterpret_cast<const uint4 *>(a.world_blob);
+    uint4 *dst = reinterpret_cast<uint4 *>(smem);
+    const int n16 = a.world_bytes / 16;
+    for (int base = w * 64; base < n16; base += nw * 64) {
+        const int k = base + lane;
+        if (k < n16) uavq::glds16(src + k, dst + base);
+    }
+}
+
 template <typename MaskT>
 __device__ __forceinline__ WorldLds<MaskT> world_view(unsigned char *smem, const StepArgs &a)
 {
@@ -1168,7 +1183,10 @@ struct CoopLds {
 // separate act launch cost 6 us plus a launch boundary in front of this kernel's 8 us.
 // PAHEAD (with POLICY): the policy's layer-1 forward with every operand of the strip requested first (116 more registers: one
 // wavefront per SIMD) -- for launches of at most one workgroup per CU, where nothing else hides an LDS round trip per K block.
-template <typename MaskT, bool APF, int OBS, bool POLICY = false, bool PAHEAD = false>
+// GLDS (with POLICY and a layer-1 image, a.pol_img): the image and the world blob come in by LDS-DMA, both requested at the top of
+// the prologue (uavq::img_glds, stage_copy_glds): no staging registers, no ds_write pass, and the world's round trip no longer
+// waits behind the image's (the register form commits the image before wavefronts 2-3 request the world).  Same LDS bytes.
+template <typename MaskT, bool APF, int OBS, bool POLICY = false, bool PAHEAD = false, bool GLDS = false>
 __global__ void __launch_bounds__(256) k_step_coop(StepArgs a)
 {
     UAV_HOT_PRIO();
@@ -1202,7 +1220,10 @@ __global__ void __launch_bounds__(256) k_step_coop(StepArgs a)
     if (POLICY) {
         const int tid = (int)threadIdx.x;
         const uavq::NetDev nl = uavq::net_view(a.pol_local, pol_n2);
-        if (a.pol_img) uavq::img_issue(vW, a.pol_img);
+        if (GLDS) {
+            uavq::img_glds(reinterpret_cast<float *>(smem + a.pol_off), a.pol_img, wv);
+            if (wv >= 2) stage_copy_glds(smem, a, wv - 2, 2);
+        } else if (a.pol_img) uavq::img_issue(vW, a.pol_img);
         else { uavq::w_issue(vW, a.pol_local); uavq::w_issue_sc(pol_sc, a.pol_local, nl.b1); }
 #pragma unroll
         for (int k = 0; k < 4; ++k) pol_w2[k] = nl.W2[tid + 256 * k < pol_n2 * uavq::kHid ? tid + 256 * k : pol_n2 * uavq::kHid - 1];
@@ -1259,7 +1280,9 @@ __global__ void __launch_bounds__(256) k_step_coop(StepArgs a)
     pre.moved = false;
     if (POLICY) {                        // policy prologue, part 2: weights into LDS
         const int tid = (int)threadIdx.x;
-        if (a.pol_img) uavq::img_commit(reinterpret_cast<float *>(smem + a.pol_off), vW); else uavq::w_commit_split(pW1, vW, pol_sc);
+        if (!GLDS) {                     // (GLDS: the image is in flight by LDS-DMA; the staging barrier waits for it)
+            if (a.pol_img) uavq::img_commit(reinterpret_cast<float *>(smem + a.pol_off), vW); else uavq::w_commit_split(pW1, vW, pol_sc);
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {    // (clamped like the loads: past the end, the last element onto itself -- no guarded stores)
             const int at = tid + 256 * k < pol_n2 * uavq::kHid ? tid + 256 * k : pol_n2 * uavq::kHid - 1;
@@ -1268,7 +1291,7 @@ __global__ void __launch_bounds__(256) k_step_coop(StepArgs a)
         if (tid < pol_n2) pb2[tid] = pol_b2v;
     }
     if (wv >= 2) {                       // the world blob comes in through waves 2 and 3 (wave 1's loads depend on
-        stage_copy(smem, a, (int)threadIdx.x - 128, 128);                    // its state loads: it would hold the barrier)
+        if (!(POLICY && GLDS)) stage_copy(smem, a, (int)threadIdx.x - 128, 128);   // its state loads: it would hold the barrier)
     } else if (wv == 0) {                             // first half of update_PathPlan: needs the agent's own state only
         unpack_flags(g);
         const bool masked = a.active && a.active[ii] == 0;
@@ -1759,7 +1782,12 @@ static void launch_step(const UavEnv *e, const StepArgs &a_in, hipStream_t s)
             a.pol_off = (int32_t)((clds + 15) & ~(size_t)15);
             const size_t plds = (size_t)a.pol_off + (size_t)(uavq::kTileF + uavq::kMaxOut * uavq::kHid + uavq::kMaxOut + 64) * 4;
             // (up to one workgroup per CU the register-hungry form of the forward; beyond, two or three workgroups share a CU)
-            if (cgrid <= 256) launch_lds((k_step_coop<MaskT, false, OBS_KIND_PACKED, true, true>), cgrid, 256, plds, s, a);
+            // (with a layer-1 image: the image and the world by LDS-DMA; UAVENV_STAGE_VGPR=1 keeps the register-staged form -- A/B knob)
+            static const bool stage_vgpr = env_int("UAVENV_STAGE_VGPR", 0) != 0;
+            if (a.pol_img && !stage_vgpr) {
+                if (cgrid <= 256) launch_lds((k_step_coop<MaskT, false, OBS_KIND_PACKED, true, true, true>), cgrid, 256, plds, s, a);
+                else launch_lds((k_step_coop<MaskT, false, OBS_KIND_PACKED, true, false, true>), cgrid, 256, plds, s, a);
+            } else if (cgrid <= 256) launch_lds((k_step_coop<MaskT, false, OBS_KIND_PACKED, true, true>), cgrid, 256, plds, s, a);
             else launch_lds((k_step_coop<MaskT, false, OBS_KIND_PACKED, true, false>), cgrid, 256, plds, s, a);
             return;
         }
