@@ -41,7 +41,7 @@ SYMBOLS = (
     "uavenv_sac_critic_adam_multi", "uavenv_sac_actor_adam_multi",
     "uavenv_per_num_chunks", "uavenv_per_rotation", "uavenv_per_rebuild", "uavenv_per_sample", "uavenv_per_set", "uavenv_per_fill", "uavenv_per_set_f32", "uavenv_per_weights", "uavenv_per_fill_frame", "uavenv_per_rebuild_frame", "uavenv_p2p_allreduce", "uavenv_sac_partial_rows_n",
     "uavenv_sac_act", "uavenv_sac_reduce", "uavenv_sac_partial_rows", "uavenv_sac_last_error", "uavenv_sac_set_debug_buffer", "uavenv_sac_critic_grad", "uavenv_sac_critic_adam", "uavenv_sac_actor_grad",
-    "uavenv_sac_actor_adam", "uavenv_fed_aggregate",
+    "uavenv_sac_actor_adam", "uavenv_fed_aggregate", "uavenv_eval_episodes",
 )
 SAC_CRITIC_IN, SAC_ACTOR_PARAMS, SAC_CRITIC_PARAMS, SAC_ACTOR_STRIDE, SAC_CRITIC_STRIDE = 102, 6724, 10882, 6728, 21768
 
@@ -68,6 +68,26 @@ class UavDqnNet(C.Structure):
     _fields_ = [("local", C.c_void_p), ("target", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
                 ("w", C.c_int32), ("hid", C.c_int32), ("n_actions", C.c_int32), ("dueling", C.c_int32),
                 ("mfma_dtype", C.c_int32), ("reserved0", C.c_int32)]
+
+
+# uavenv_eval_episodes (include/uavenv.h): outcome codes, the 64-byte per-episode record and the call's arguments
+EVAL_SUCCESS, EVAL_LOSE, EVAL_TRUNCATED, EVAL_INVALID = 1, 2, 4, 5
+EVAL_RECORD_BYTES = 64
+
+
+class UavEvalRecord(C.Structure):
+    _fields_ = [("ret", C.c_double), ("total_score", C.c_double), ("path_len", C.c_double), ("energy", C.c_double),
+                ("v0x", C.c_double), ("v0y", C.c_double), ("steps", C.c_int32), ("subgoals", C.c_int32),
+                ("collisions", C.c_int32), ("outcome", C.c_uint8), ("reach_goal", C.c_uint8), ("slot", C.c_uint8),
+                ("reserved", C.c_uint8)]
+
+
+class UavEvalArgs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("first", C.c_int32), ("start_goal", C.c_void_p), ("sub", C.c_void_p),
+                ("nsub", C.c_void_p), ("m", C.c_int32), ("max_steps", C.c_int32), ("v0", C.c_void_p),
+                ("seed", C.c_uint64), ("eps", C.c_float), ("traj_steps", C.c_int32), ("records", C.c_void_p),
+                ("traj_pos", C.c_void_p), ("traj_act", C.c_void_p), ("max_workgroups", C.c_int32),
+                ("reserved0", C.c_int32)]
 
 
 class UavPer(C.Structure):
@@ -381,6 +401,8 @@ def load() -> C.CDLL:
     lib.uavenv_per_fill_frame_strided.argtypes = [per, i64, i64, f64, vp, i64, i64, vp]
     lib.uavenv_fed_aggregate.restype = C.c_int
     lib.uavenv_fed_aggregate.argtypes = [vp, i32, i32, f32, vp]
+    lib.uavenv_eval_episodes.restype = C.c_int
+    lib.uavenv_eval_episodes.argtypes = [vp, C.POINTER(UavDqnNet), C.POINTER(UavEvalArgs), vp]
     if lib.uavenv_abi_version() != ABI_VERSION:
         raise UavEnvError(f"libuavenv ABI {lib.uavenv_abi_version()} != binding {ABI_VERSION}")
     _LIB = lib

@@ -188,6 +188,7 @@ struct UavEnv {
     bool rp_commit_recorded = false;
     int world_gen = 0, rp_world_gen = 0;
     long long rp_calls = 0, rp_rows_planned = 0;
+    float *eval_img = nullptr;         // uavenv_eval_episodes: the net's layer-1 image (2 x UAVENV_DQN_IMAGE_FLOATS), allocated on first use
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1620,6 +1621,216 @@ __global__ void k_get_state(StepArgs a, int first, int count, double *__restrict
 }
 
 // ------------------------------------------------------------------------------------------------
+// Greedy policy evaluation (uavenv_eval_episodes): whole episodes in one launch.
+// Persistent workgroups of four wavefronts.  The world blob and the policy's layer-1 image come in once per workgroup by
+// LDS-DMA (stage_copy_glds, uavq::img_glds), fc2 / b2 through registers; after that staging barrier the wavefronts run on their
+// own (no further workgroup barrier) and nothing per step touches memory but the scenario's sub-goal rows, the records and the
+// optional trajectory.  Lane = episode: one wavefront keeps 64 episodes in flight; a lane whose episode ended stores its record
+// and installs episode e + L (L = lanes of the grid: a static stride, no atomics), so a record does not depend on where, or next
+// to which episodes, it ran.  One iteration = one step of every live lane, in the order of the composed launches:
+//   state_PathPlan of the current state (obs_bits_queued, wave-collective) -> the packed row in registers -> Q(s) -> action
+//   -> update_PathPlan (step_pre / step_post, non-APF) -> record + reset into the next episode where the episode ended.
+// Q(s): k_dqn_act_packed's forward.  The 64 rows go through a wave-private LDS slot; strip st (rows of lanes 16 st .. 16 st + 15)
+// is fwd_strip_split + w2_load / q_strip as there (same operands in the same K positions, same MFMA order: the same Q values), and
+// lane 16 st + r keeps strip st's result.  The forward runs wave-uniformly every iteration; idle lanes feed a zero row.
+// ------------------------------------------------------------------------------------------------
+struct EvalArgs {
+    const float *img;                  // q_local's layer 1 in the split form (uavenv_dqn_split_image)
+    const float *local;                // q_local's flat block (fc2 / b2 are read from it)
+    const double *v0;                  // nullable [n][2]
+    uint4 *rec;                        // [n] x 64 bytes (UavEvalRecord)
+    double *traj_pos;                  // nullable [n][traj_steps + 1][3]
+    int8_t *traj_act;                  // nullable [n][traj_steps]
+    uint64_t seed;
+    float eps;
+    int32_t n, first, max_steps, traj_steps, lanes;
+    int32_t n2, dueling;
+    int32_t img_off, w2_off, slot_off, slot_bytes;   // LDS byte offsets: image, fc2 (+ b2), per-wave slots
+};
+
+struct EvalLane {
+    int e;                             // episode (>= n: the lane is idle)
+    int steps, collisions, cap;        // cap: the natural bound n_sub x Max_Step + 1
+    double ret, energy, v0x, v0y;
+};
+
+__device__ __forceinline__ void eval_store_record(const EvalArgs &v, int e, const Agent &g, const EvalLane &L, int outcome, int slot)
+{
+    uint4 *dst = v.rec + (size_t)e * 4;
+    const unsigned long long r = (unsigned long long)__double_as_longlong(L.ret), t = (unsigned long long)__double_as_longlong(g.total);
+    const unsigned long long p = (unsigned long long)__double_as_longlong(g.path_len), en = (unsigned long long)__double_as_longlong(L.energy);
+    const unsigned long long vx = (unsigned long long)__double_as_longlong(L.v0x), vy = (unsigned long long)__double_as_longlong(L.v0y);
+    dst[0] = make_uint4((uint32_t)r, (uint32_t)(r >> 32), (uint32_t)t, (uint32_t)(t >> 32));
+    dst[1] = make_uint4((uint32_t)p, (uint32_t)(p >> 32), (uint32_t)en, (uint32_t)(en >> 32));
+    dst[2] = make_uint4((uint32_t)vx, (uint32_t)(vx >> 32), (uint32_t)vy, (uint32_t)(vy >> 32));
+    dst[3] = make_uint4((uint32_t)L.steps, (uint32_t)g.sub_idx, (uint32_t)L.collisions,
+                        (uint32_t)outcome | ((uint32_t)(g.reach ? 1 : 0) << 8) | ((uint32_t)slot << 16));
+}
+
+// the first episode at or after L.e whose scenario row is valid: UAV.reset() into `g` (invalid rows get their record here)
+__device__ __forceinline__ void eval_install(const StepArgs &a, const EvalArgs &v, Agent &g, EvalLane &L)
+{
+    int row = 0;
+    while (L.e < v.n) {
+        row = (int)(((int64_t)v.first + L.e) % a.bank.m);
+        const int nt = a.bank.nsub[row];
+        if (nt >= 0 && nt <= a.K) break;
+        Agent z = {};
+        EvalLane zl = {};
+        eval_store_record(v, L.e, z, zl, UAVENV_EVAL_INVALID, L.e % a.U);
+        L.e += v.lanes;
+    }
+    if (L.e >= v.n) return;
+    ResetCand c;
+    c.scn = row;
+    reset_candidate_fetch(a, c);
+    double vx, vy;
+    if (v.v0) {
+        vx = v.v0[(size_t)L.e * 2];
+        vy = v.v0[(size_t)L.e * 2 + 1];
+    } else {                           // reset_candidate_draw's heading with this call's own key
+        const uint4 r = philox4x32_10(make_uint4((uint32_t)L.e, 0u, 0u, 0xe7a1u), make_uint2((uint32_t)v.seed, (uint32_t)(v.seed >> 32)));
+        double sn, cs;
+        sincos(kTwoPi * u53(r.x, r.y), &sn, &cs);
+        vx = a.max_v * cs;
+        vy = a.max_v * sn;
+    }
+    L.v0x = vx;
+    L.v0y = vy;
+    c.f[14] = calc_v(vx, vy, a.max_v);   // reset_candidate_finish from its velocity on (calc_angle's body, inline)
+    c.f[12] = vx;
+    c.f[13] = vy;
+    c.f[15] = angle_of<true>(vx, vy);
+    apply_reset<false>(a, L.e, g, c);
+    L.steps = 0;
+    L.collisions = 0;
+    L.cap = c.n_total * a.max_step + 1;
+    L.ret = 0.0;
+    L.energy = 0.0;
+    if (v.traj_steps > 0) {
+        double *p = v.traj_pos + (size_t)L.e * (v.traj_steps + 1) * 3;
+        p[0] = g.o.px; p[1] = g.o.py; p[2] = g.o.pz;
+    }
+}
+
+template <typename MaskT>
+__global__ void __launch_bounds__(256, 1) k_eval_episodes(StepArgs a, EvalArgs v)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int lane = (int)threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int tid = (int)threadIdx.x;
+    // ---- staging, once per workgroup: the image and the world by LDS-DMA, fc2 / b2 through registers
+    float *img = reinterpret_cast<float *>(smem + v.img_off);
+    float *W2 = reinterpret_cast<float *>(smem + v.w2_off);        // [16][64]
+    float *b2 = W2 + uavq::kMaxOut * uavq::kHid;                    // [16]
+    uavq::img_glds(img, v.img, wv);
+    if (wv >= 2) stage_copy_glds(smem, a, wv - 2, 2);               // (as k_step_coop: the world through wavefronts 2-3)
+    {
+        const uavq::NetDev nl = uavq::net_view(v.local, v.n2);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (tid + 256 * k < v.n2 * uavq::kHid) W2[tid + 256 * k] = nl.W2[tid + 256 * k];
+        if (tid < v.n2) b2[tid] = nl.b2[tid];
+    }
+    Agent g = {};
+    EvalLane L = {};
+    L.e = (int)blockIdx.x * 256 + tid;                               // this lane's first episode (installed at the loop's top)
+    bool install = true;
+    __syncthreads();                                                 // world, image, fc2 staged
+    const WorldLds<MaskT> w = world_view<MaskT>(smem, a);
+    const uavq::W1Split W1 = uavq::w1split_at(img);
+    unsigned char *slot = smem + v.slot_off + wv * v.slot_bytes;
+    ObsWaveLds *Q = reinterpret_cast<ObsWaveLds *>(slot);           // the observation work queue, then (same bytes) the rows
+    uint32_t *rows = reinterpret_cast<uint32_t *>(slot);
+    const int r16 = lane & 15, grp = lane >> 4;
+    const int A = a.n_actions;
+    for (;;) {
+        if (install) eval_install(a, v, g, L);                       // (one call site: the installation is inlined once)
+        install = false;
+        if (__ballot(L.e < v.n) == 0ull) break;
+        const bool have = L.e < v.n;
+        // ---- 1. state_PathPlan of the current state, as a packed row (store_obs_row_packed's layout) in registers
+        const ObsBits bits = obs_bits_queued(w, Q, g.o.px, g.o.py, g.o.pz, have);
+        const ObsScalars sc = obs_scalars(g.o, g.head);
+        uavq::PRow R;
+        ctile_mask_words(bits, R.m0, R.m1, R.m2);
+#pragma unroll
+        for (int k = 0; k < 11; ++k) R.sc[k] = sc.f[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) R.sg[k] = sc.f[11 + k];
+        if (!have) {                                                 // idle lane: a zero row, result discarded
+            R.m0 = R.m1 = R.m2 = 0u;
+#pragma unroll
+            for (int k = 0; k < 11; ++k) R.sc[k] = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) R.sg[k] = 0.0f;
+        }
+        wave_lds_sync();                                             // (the queue's last reads are done: the rows take its bytes)
+        uavq::prow_store_lds(rows + lane * kPackedDwords, R);
+        wave_lds_sync();
+        // ---- 2. Q(s) of the 64 rows: four 16-row strips, lane 16 st + r keeps strip st
+        float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+        for (int st = 0; st < 4; ++st) {
+            uavq::PRow Rs;
+            uavq::prow_load(Rs, rows + (16 * st + r16) * kPackedDwords);
+            uavq::floatx4 h[4];
+            uavq::fwd_strip_split<false>(W1, Rs, h);
+            uavq::W2Frag<4> F;
+            uavq::w2_load<4>(F, W2, b2, v.n2);
+            float qs[4];
+            uavq::q_strip<4>(h, F, v.n2, A, v.dueling, qs);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q[k] = grp == st ? qs[k] : q[k];
+        }
+        wave_lds_sync();                                             // the rows are read: the next iteration's queue may take the bytes
+        if (have) {
+            // ---- the action: k_dqn_act_packed's greedy branch (first maximum, strict >); eps > 0: a uniform action on a draw < eps
+            int act = 0;
+            float bq = q[0];
+#pragma unroll
+            for (int k = 1; k < 4; ++k)
+                if (k < A && q[k] > bq) { bq = q[k]; act = k; }
+            if (v.eps > 0.0f) {
+                const uint4 rn = philox4x32_10(make_uint4((uint32_t)L.e, (uint32_t)L.steps, 0u, 0xe75fu),
+                                               make_uint2((uint32_t)v.seed, (uint32_t)(v.seed >> 32)));
+                const float u = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
+                if (u < v.eps) act = (int)(((uint64_t)rn.y * (uint64_t)A) >> 32);
+            }
+            // ---- 3. update_PathPlan (UAV.py:397-513): step_agent's pieces
+            const int j = L.e % a.U;
+            const double a0 = decode_action(RawAction{(uint32_t)act, 0u}, UAVENV_ACT_INDEX_I32, A);
+            PreStep P;
+            step_pre(a, a0, g, P);
+            if (P.moved) g.head = angle_of<true>(g.o.vx, g.o.vy);   // :423
+            double r = 0.0;
+            int ret_done = 0, info = UAVENV_INFO_NORMAL;
+            bool head_set = false;
+            step_post<MaskT, false, true>(a, w, L.e, a0, g, P, r, ret_done, info, head_set);
+            g.o.n_rem = g.n_total - g.sub_idx;
+            L.steps += 1;
+            L.ret += r;
+            L.energy += fly_power(a.pw, g.o.V, j);
+            // a move always changes x or y (|V_vector| = Max_V > 0): the position is back where it was only after :425-428
+            if (P.moved && g.o.px == P.ox && g.o.py == P.oy && g.o.pz == P.oz) L.collisions += 1;
+            if (L.steps <= v.traj_steps) {
+                double *p = v.traj_pos + ((size_t)L.e * (v.traj_steps + 1) + L.steps) * 3;
+                p[0] = g.o.px; p[1] = g.o.py; p[2] = g.o.pz;
+                v.traj_act[(size_t)L.e * v.traj_steps + L.steps - 1] = (int8_t)act;
+            }
+            // ---- 4. the end of the episode: record, then the next episode of this lane
+            const bool trunc = (v.max_steps > 0 && L.steps >= v.max_steps) || L.steps >= L.cap;
+            if (g.done || trunc) {
+                const int outcome = g.done ? (info == UAVENV_INFO_LOSE ? UAVENV_EVAL_LOSE : UAVENV_EVAL_SUCCESS) : UAVENV_EVAL_TRUNCATED;
+                eval_store_record(v, L.e, g, L, outcome, j);
+                L.e += v.lanes;
+                install = true;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 static bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
@@ -1887,6 +2098,7 @@ int uavenv_destroy(UavEnv *e)
     (void)hipFree(e->rp_counters);
     if (e->rp_done) (void)hipEventDestroy(e->rp_done);
     if (e->rp_committed) (void)hipEventDestroy(e->rp_committed);
+    (void)hipFree(e->eval_img);
     delete e;
     return UAVENV_OK;
 }
@@ -2533,6 +2745,100 @@ int uavenv_threaten_rate(UavEnv *e, const double *xyz, uint8_t *out, int64_t n, 
 int uavenv_threaten_rate_allpairs(UavEnv *e, const double *xyz, uint8_t *out, int64_t n, void *stream)
 {
     return threaten_impl(e, xyz, out, n, stream, true);
+}
+
+int uavenv_eval_episodes(UavEnv *e, const UavDqnNet *net, const UavEvalArgs *args, void *stream)
+{
+    if (!e || !net || !args) return fail(UAVENV_EINVAL, "null argument");
+    const UavEvalArgs &u = *args;
+    if (e->cfg.apf_enabled == 1) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: APF envs are not supported");
+    if (!e->have_world) return fail(UAVENV_EINVAL, "uavenv_eval_episodes before uavenv_set_buildings");
+    const int n2 = net->n_actions + (net->dueling ? 1 : 0);
+    if (!net->local || net->mfma_dtype != UAVENV_MFMA_F32 || net->w != uavq::kW || net->hid != uavq::kHid || net->n_actions < 2 ||
+        n2 > 4 || net->n_actions != e->cfg.n_actions)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes: needs an f32-MFMA net of w %d, hid %d, the env's %d actions, <= 4 outputs",
+                    uavq::kW, uavq::kHid, e->cfg.n_actions);
+    if (u.n <= 0 || u.first < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: n %d, first %d", u.n, u.first);
+    if (!u.records || ((((uintptr_t)u.records) | ((uintptr_t)net->local)) & 15u) != 0)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes: records and net->local must be 16-byte aligned device pointers");
+    const int given = (u.start_goal ? 1 : 0) + (u.sub ? 1 : 0) + (u.nsub ? 1 : 0);
+    if (given != 0 && given != 3) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: give all three scenario arrays or none");
+    if (given == 3 && u.m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: m %d", u.m);
+    if (given == 0 && e->bank_m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: no scenarios (the env has no bank)");
+    if (u.traj_steps < 0 || u.traj_steps >= (1 << 30) || (u.traj_steps > 0 && (!u.traj_pos || !u.traj_act)))
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes: traj_steps %d needs both trajectory pointers", u.traj_steps);
+    if (u.max_steps < 0 || u.max_workgroups < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: max_steps / max_workgroups < 0");
+    if ((((uintptr_t)u.start_goal) | ((uintptr_t)u.sub) | ((uintptr_t)u.v0) | ((uintptr_t)u.traj_pos)) & 7u)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes: misaligned f64 array");
+    if (((uintptr_t)u.nsub) & 3u) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: misaligned nsub");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!e->eval_img) HIP_TRY(hipMalloc((void **)&e->eval_img, 2 * UAVENV_DQN_IMAGE_FLOATS * sizeof(float)));
+    UavDqnNet img_net = *net;
+    img_net.target = net->local;       // (the image call converts two nets: q_local twice, the first half is used)
+    const int rc = uavenv_dqn_split_image(&img_net, e->eval_img, stream);
+    if (rc != UAVENV_OK) return fail(rc, "uavenv_eval_episodes: layer-1 image");
+
+    // the env's parameters and world; the scenario set in the bank's place; nothing the step launches own
+    StepArgs a = base_args(e);
+    a.moved_word = nullptr;
+    a.meta = nullptr;
+    a.meta_a1 = nullptr;
+    a.dbg = nullptr;
+    a.block = 256;
+    if (given == 3) {
+        a.bank.start_goal = u.start_goal;
+        a.bank.sub = u.sub;
+        a.bank.nsub = u.nsub;
+        a.bank.m = u.m;
+    }
+    EvalArgs v;
+    memset(&v, 0, sizeof(v));
+    v.img = e->eval_img;
+    v.local = net->local;
+    v.v0 = u.v0;
+    v.rec = reinterpret_cast<uint4 *>(u.records);
+    v.traj_pos = u.traj_steps > 0 ? u.traj_pos : nullptr;
+    v.traj_act = u.traj_steps > 0 ? u.traj_act : nullptr;
+    v.seed = u.seed;
+    v.eps = u.eps;
+    v.n = u.n;
+    v.first = u.first;
+    v.max_steps = u.max_steps;
+    v.traj_steps = u.traj_steps;
+    v.n2 = n2;
+    v.dueling = net->dueling;
+    v.img_off = (e->world_bytes + 15) & ~15;
+    v.w2_off = v.img_off + uavq::kSplitF * 4;
+    v.slot_off = (v.w2_off + (uavq::kMaxOut * uavq::kHid + uavq::kMaxOut) * 4 + 15) & ~15;
+    int slot = (int)sizeof(ObsWaveLds);            // the work queue, then (same bytes) the wavefront's 64 packed rows
+    if (slot < 64 * kPackedDwords * 4) slot = 64 * kPackedDwords * 4;
+    v.slot_bytes = (slot + 15) & ~15;
+    const size_t lds = (size_t)v.slot_off + 4 * (size_t)v.slot_bytes;
+    const void *fn = e->mask_bytes == 4 ? reinterpret_cast<const void *>(k_eval_episodes<uint32_t>)
+                                        : reinterpret_cast<const void *>(k_eval_episodes<uint64_t>);
+    if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // grid: as many workgroups as stay resident, at most one per 256 episodes (or max_workgroups)
+    const int want = (int)(((int64_t)u.n + 255) / 256);
+    int grid = want;
+    if (u.max_workgroups > 0) {
+        grid = u.max_workgroups < want ? u.max_workgroups : want;
+    } else {
+        int per_cu = 0, cus = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
+        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device));
+        const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+        if (resident < grid) grid = (int)resident;
+    }
+    if (grid < 1) grid = 1;
+    v.lanes = grid * 256;
+    // (a lane's next episode is e + lanes in 32-bit arithmetic: the last one taken must still be representable)
+    if ((int64_t)u.n + (int64_t)v.lanes > (int64_t)INT32_MAX)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes: n %d + %d lanes exceeds the episode index range", u.n, v.lanes);
+    if (e->mask_bytes == 4) hipLaunchKernelGGL(k_eval_episodes<uint32_t>, dim3(grid), dim3(256), lds, s, a, v);
+    else hipLaunchKernelGGL(k_eval_episodes<uint64_t>, dim3(grid), dim3(256), lds, s, a, v);
+    HIP_TRY(hipGetLastError());
+    return UAVENV_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,172 @@
+"""Greedy policy evaluation: whole DQN episodes in one GPU launch (csrc/uavenv.hip k_eval_episodes, include/uavenv.h
+uavenv_eval_episodes).
+
+The reference meant to have this (Envs/PathPlan_City.py:349-351 Evaluation_Action, :543-552 run_XML_scene / Load_Scene_FromXML)
+and acts greedily when Is_Train == 0 (Trainer/DuelingDQN_Trainer.py:90).  Episode e flies scenario row (first + e) mod m of a
+scenario set -- the env's reset bank, or a held-out set (held_out_scenarios) -- with the greedy action of the learner's q_local,
+and leaves one 64-byte record.  The env's agents, tick and replay are not touched: evaluating between training calls does not
+change the training run.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+
+RECORD_DTYPE = np.dtype([("ret", "<f8"), ("total_score", "<f8"), ("path_len", "<f8"), ("energy", "<f8"), ("v0x", "<f8"),
+                         ("v0y", "<f8"), ("steps", "<i4"), ("subgoals", "<i4"), ("collisions", "<i4"), ("outcome", "u1"),
+                         ("reach_goal", "u1"), ("slot", "u1"), ("reserved", "u1")])
+assert RECORD_DTYPE.itemsize == _lib.EVAL_RECORD_BYTES
+OUTCOMES = {"success": _lib.EVAL_SUCCESS, "lose": _lib.EVAL_LOSE, "truncated": _lib.EVAL_TRUNCATED,
+            "invalid": _lib.EVAL_INVALID}
+
+
+def summarize(rec: np.ndarray) -> dict:
+    """Counts and means of a structured array of RECORD_DTYPE (the means over the valid episodes)."""
+    rec = np.asarray(rec)
+    out = {"episodes": int(len(rec))}
+    for name, code in OUTCOMES.items():
+        out[name] = int((rec["outcome"] == code).sum())
+    valid = rec[rec["outcome"] != _lib.EVAL_INVALID]
+    nv = len(valid)
+    out["success_rate"] = out["success"] / nv if nv else 0.0
+    out["lose_rate"] = out["lose"] / nv if nv else 0.0
+
+    def mean(field):
+        return float(valid[field].astype(np.float64).mean()) if nv else 0.0
+
+    out["mean_return"] = mean("ret")
+    out["mean_steps"] = mean("steps")
+    out["mean_path_len"] = mean("path_len")
+    out["mean_energy"] = mean("energy")
+    out["mean_subgoals"] = mean("subgoals")
+    out["mean_collisions"] = mean("collisions")
+    out["average_score"] = mean("total_score")
+    return out
+
+
+@dataclass
+class EvalResult:
+    """records: uint8 device tensor [n, 64] (UavEvalRecord); positions / actions: the optional trajectory, device tensors
+    [n, T + 1, 3] f64 (NaN past an episode's end) and [n, T] int8 (-1 past the end)."""
+    records: object
+    positions: Optional[object] = None
+    actions: Optional[object] = None
+
+    def host_records(self) -> np.ndarray:
+        return self.records.cpu().numpy().reshape(-1).view(RECORD_DTYPE)
+
+    def summary(self) -> dict:
+        return summarize(self.host_records())
+
+
+def _check_args(n_episodes, first, eps, max_steps, trajectory_steps, max_workgroups):
+    if int(n_episodes) != n_episodes or n_episodes <= 0:
+        raise ValueError(f"n_episodes must be a positive integer (got {n_episodes!r})")
+    if int(first) != first or first < 0:
+        raise ValueError(f"first must be a non-negative integer (got {first!r})")
+    if not np.isfinite(eps) or eps < 0.0 or eps > 1.0:
+        raise ValueError(f"eps must lie in [0, 1] (got {eps!r})")
+    for name, val in (("max_steps", max_steps), ("trajectory_steps", trajectory_steps), ("max_workgroups", max_workgroups)):
+        if int(val) != val or val < 0:
+            raise ValueError(f"{name} must be a non-negative integer (got {val!r})")
+
+
+def _check_scenarios(scenarios, K):
+    if scenarios is None:
+        return None
+    if len(scenarios) < 3:
+        raise ValueError("scenarios = (start_goal [m,6], sub_goals [m,K,3], n_sub [m]), e.g. env.rrt_plan(...)[:3]")
+    sg, sub, ns = scenarios[0], scenarios[1], scenarios[2]
+    m = int(sg.shape[0]) if hasattr(sg, "shape") else -1
+    if m <= 0 or tuple(sg.shape) != (m, 6) or tuple(sub.shape) != (m, K, 3) or tuple(ns.shape) != (m,):
+        raise ValueError(f"scenario arrays must be [m,6], [m,{K},3], [m] with m > 0")
+    return m
+
+
+def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int = 0, seed: int = 0, eps: float = 0.0,
+                    max_steps: int = 0, v0=None, trajectory_steps: int = 0, max_workgroups: int = 0) -> EvalResult:
+    """n_episodes greedy episodes of learner.q_local (a FusedDQNLearner on the f32 MFMA) on env (a VecPathPlanEnv, APF off).
+
+    scenarios: None (the env's bank) or (start_goal [m,6] f64, sub_goals [m,K,3] f64, n_sub [m] i32) device tensors, e.g.
+    held_out_scenarios(env, m, seed).  v0: [n,2] raw initial V_vector per episode (default: headings from Philox(seed, e)).
+    eps > 0 takes a uniform action with probability eps (eps = 1: the random policy).  max_steps > 0 truncates.  Enqueued on
+    the current stream; the records are read when summary() / host_records() is called."""
+    # every check first: nothing is read from the device or enqueued before the arguments are known to be good
+    _check_args(n_episodes, first, eps, max_steps, trajectory_steps, max_workgroups)
+    m = _check_scenarios(scenarios, env.K)
+    n, T = int(n_episodes), int(trajectory_steps)
+    if getattr(learner, "net", None) is None:
+        raise ValueError("evaluate_policy needs a fused learner (FusedDQNLearner)")
+    if v0 is not None and tuple(np.shape(v0)) != (n, 2):
+        raise ValueError(f"v0 must be [{n}, 2] (got {tuple(np.shape(v0))})")
+    import torch
+    dev = env.device
+    if v0 is not None:
+        v0 = torch.as_tensor(v0, dtype=torch.float64, device=dev).contiguous()
+    if scenarios is not None:
+        sg = torch.as_tensor(scenarios[0], dtype=torch.float64, device=dev).contiguous()
+        sub = torch.as_tensor(scenarios[1], dtype=torch.float64, device=dev).contiguous()
+        ns = torch.as_tensor(scenarios[2], dtype=torch.int32, device=dev).contiguous()
+    records = torch.zeros((n, _lib.EVAL_RECORD_BYTES), dtype=torch.uint8, device=dev)
+    pos = act = None
+    if T > 0:
+        pos = torch.full((n, T + 1, 3), float("nan"), dtype=torch.float64, device=dev)
+        act = torch.full((n, T), -1, dtype=torch.int8, device=dev)
+    a = _lib.UavEvalArgs()
+    a.n, a.first = n, int(first)
+    if scenarios is not None:
+        a.start_goal, a.sub, a.nsub, a.m = sg.data_ptr(), sub.data_ptr(), ns.data_ptr(), m
+    a.max_steps = int(max_steps)
+    a.v0 = None if v0 is None else v0.data_ptr()
+    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.eps = float(eps)
+    a.traj_steps = T
+    a.records = records.data_ptr()
+    a.traj_pos = None if pos is None else pos.data_ptr()
+    a.traj_act = None if act is None else act.data_ptr()
+    a.max_workgroups = int(max_workgroups)
+    _lib.check(env.lib.uavenv_eval_episodes(env._h, C.byref(learner.net), C.byref(a), env._stream()), "uavenv_eval_episodes")
+    res = EvalResult(records, pos, act)
+    res._keep = (v0, scenarios if scenarios is None else (sg, sub, ns))   # alive until the launch has read them
+    return res
+
+
+def slot_scenarios(scenarios, uav_per_env: int, max_v: float, seed: int):
+    """Every row r of a scenario set repeated uav_per_env times (at r * U + j) with ONE initial heading per row, drawn from
+    numpy's PCG64 on `seed`: episode r * U + j then flies mission r, from the same start, heading and path, as UAV slot j
+    (slot = episode mod U), so the slots' results compare mission for mission.  -> ((start_goal, sub_goals, n_sub), v0) with
+    v0 = the raw initial V_vector [m * U, 2]."""
+    import torch
+    sg, sub, ns = scenarios
+    U = int(uav_per_env)
+    if U <= 0:
+        raise ValueError(f"uav_per_env must be positive (got {uav_per_env!r})")
+    m = int(sg.shape[0])
+    t = np.random.default_rng(int(seed)).uniform(0.0, 2.0 * np.pi, m)
+    v0 = np.repeat(np.stack([max_v * np.cos(t), max_v * np.sin(t)], 1), U, axis=0)
+    rep = tuple(torch.as_tensor(x).repeat_interleave(U, dim=0).contiguous() for x in (sg, sub, ns))
+    return rep, torch.as_tensor(v0, dtype=torch.float64, device=rep[0].device)
+
+
+def held_out_scenarios(env, m: int, seed: int, max_iter: int = 10000):
+    """The first m valid rows (2 <= n_sub <= K) of the GPU planner on `seed` -- pick a seed the training bank never used.
+    n_sub = 1 is the planner's give-up marker (a path of [goal] only, csrc/rrt.hip) and n_sub < 0 a path longer than K."""
+    if int(m) != m or m <= 0:
+        raise ValueError(f"m must be a positive integer (got {m!r})")
+    import torch
+    sgs, subs, nss, have, k = [], [], [], 0, 0
+    while have < m:
+        ask = max(2 * (m - have), 1024)
+        sg, sub, ns, _ = env.rrt_plan(ask, seed=int(seed) + k * 0x9E3779B1, max_iter=max_iter)
+        ok = (ns >= 2) & (ns <= env.K)
+        sgs.append(sg[ok]); subs.append(sub[ok]); nss.append(ns[ok])
+        have += int(ok.sum())
+        k += 1
+        if k >= 8 and have < m:
+            raise RuntimeError(f"held_out_scenarios: only {have} of {m} planned paths are valid after {k} rounds")
+    return torch.cat(sgs)[:m].contiguous(), torch.cat(subs)[:m].contiguous(), torch.cat(nss)[:m].contiguous()

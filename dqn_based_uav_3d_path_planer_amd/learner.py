@@ -492,6 +492,11 @@ class FusedDQNLearner:
                                      None if q_out is None else q_out.data_ptr(), self._stream())
         _lib.check(rc, "uavenv_dqn_act")
 
+    def evaluate(self, env, n_episodes: int, **kw):
+        """Greedy evaluation of q_local: evaluate.evaluate_policy(env, self, n_episodes, **kw)."""
+        from .evaluate import evaluate_policy
+        return evaluate_policy(env, self, n_episodes, **kw)
+
     def learn_from_ring(self, ring, batch: int, seed: int, counter: int, explicit_idx: torch.Tensor = None,
                         is_weights: torch.Tensor = None, abs_td_out: torch.Tensor = None):
         """One learn_off_policy() on `batch` transitions drawn from the device ring (same draws as ring.sample).

@@ -397,6 +397,56 @@ int uavenv_dqn_reduce_adam(const UavDqnNet *net, const float *partials_dev, int3
 int uavenv_dqn_act(const UavDqnNet *net, const void *obs_dev, int32_t obs_dtype, int32_t n, float eps, uint64_t seed,
                    uint64_t counter, int32_t *index_out_dev, float *steer_out_dev, float *q_out_dev, void *stream);
 
+/* ---- greedy policy evaluation: whole episodes in one launch (Trainer/DuelingDQN_Trainer.py:90, Is_Train == 0) ----------------
+ * Episode e (0 <= e < n) flies scenario row (first + e) mod m of a scenario set -- the env's bank (start_goal / sub / nsub NULL) or
+ * caller arrays in the bank's layout (start_goal [m][6], sub [m][K][3], nsub [m], K = the env's max_subgoals) -- as UAV slot
+ * j = e mod uav_per_env (whose power parameters price the energy).  The reset is UAV.reset() as the bank reset does it (non-APF;
+ * alias = nsub >= 2).  Initial V_vector: v0 [n][2] (raw, before Calc_V) or Max_V (cos t, sin t) with t ~ U[0, 2 pi) from Philox
+ * keyed by (seed; e, 0, 0, 0xe7a1) (the bank reset's key constant is 0x5eed).  Every step: state_PathPlan of the current state,
+ * the packed row's Q(s) by the forward of uavenv_dqn_act on packed rows (f32 MFMA: bit-identical Q values), the first maximum
+ * (strict >) -- with eps > 0 a uniform action where the 24-bit draw of Philox (seed; e, step, 0, 0xe75f) is < eps --, then
+ * update_PathPlan (UAV.py:397-513).  The episode ends when the agent is done (success / lose), after max_steps > 0 steps
+ * (truncated) or at the natural bound n_sub x Max_Step + 1; a popped sub-goal ("done" returned, agent not done) does not end it.
+ * The call never reads or writes the env's agents, its tick, a pending uavenv_set_step_meta or the moved word: a training run is
+ * the same with or without evaluations between its calls.  Calls on one env run in stream order (they share the env's layer-1
+ * image scratch).  Takes non-APF envs with a world, f32-MFMA nets of the uavenv_step_policy shape (w 100, hid 64, the env's
+ * n_actions >= 2, at most 4 layer-2 outputs); UAVENV_EINVAL otherwise, and for n <= 0, first < 0, misaligned pointers (16 bytes:
+ * net->local, records), caller scenarios with m <= 0 or only some of the three pointers, no scenarios at all, traj_steps > 0
+ * without both trajectory pointers (or >= 2^30), or n so large that n + the grid's lanes exceeds INT32_MAX. */
+#define UAVENV_EVAL_SUCCESS 1       /* the agent reached the goal (or had no sub-goal left) */
+#define UAVENV_EVAL_LOSE 2          /* Step reached Max_Step */
+#define UAVENV_EVAL_TRUNCATED 4     /* stopped by max_steps (or the natural bound) before the agent was done */
+#define UAVENV_EVAL_INVALID 5       /* the scenario row has nsub < 0 or nsub > K: not flown, 0 steps */
+typedef struct UavEvalRecord {     /* 64 bytes per episode */
+    double ret;                     /* sum of the rewards update_PathPlan returned, in step order from 0.0 */
+    double total_score, path_len;   /* the agent's fields at the end (as uavenv_get_state reports them) */
+    double energy;                  /* sum of Calc_Fly_Power over the steps (as uavenv_step's energy64) */
+    double v0x, v0y;                /* the raw initial V_vector of the reset */
+    int32_t steps;                  /* update_PathPlan calls */
+    int32_t subgoals;               /* sub-goals popped */
+    int32_t collisions;             /* steps that took the Threaten_rate == 1 branch (UAV.py:425-428) */
+    uint8_t outcome;                /* UAVENV_EVAL_* */
+    uint8_t reach_goal, slot, reserved;
+} UavEvalRecord;
+typedef struct UavEvalArgs {
+    int32_t n, first;               /* episodes; scenario row of episode e = (first + e) mod m */
+    const double *start_goal;       /* dev, nullable (all three NULL: the env's bank) [m][6] */
+    const double *sub;              /* dev [m][K][3] */
+    const int32_t *nsub;            /* dev [m] */
+    int32_t m;                      /* rows of the caller's set (ignored for the bank) */
+    int32_t max_steps;              /* > 0: truncate after this many steps */
+    const double *v0;               /* dev, nullable [n][2] raw initial V_vector per episode */
+    uint64_t seed;                  /* headings (v0 NULL) and exploration draws */
+    float eps;                      /* <= 0: greedy, no draws; 1: the uniform random policy */
+    int32_t traj_steps;             /* > 0: trajectory of the first traj_steps steps */
+    UavEvalRecord *records;         /* dev [n], 16-byte aligned */
+    double *traj_pos;               /* dev [n][traj_steps + 1][3]: the start, then the position after each step */
+    int8_t *traj_act;               /* dev [n][traj_steps]: the action of each step */
+    int32_t max_workgroups;         /* 0: as many as stay resident, at most ceil(n / 256); > 0: at most this many */
+    int32_t reserved0;
+} UavEvalArgs;
+int uavenv_eval_episodes(UavEnv *env, const UavDqnNet *net, const UavEvalArgs *args, void *stream);
+
 /* ---- multi-GPU: one-shot all-reduce of the gradient bucket over peer-mapped HBM (csrc/p2p.hip) ------------------- */
 /* One UavP2P per rank (= per GPU / process).  create -> every rank publishes its UAVENV_P2P_HANDLE_BYTES handle
  * (uavenv_p2p_handle) -> the `world` handles, in rank order, go to uavenv_p2p_connect on every rank.  Then, per update,

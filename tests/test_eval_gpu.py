@@ -1,0 +1,410 @@
+"""Greedy policy evaluation on the device (uavenv_eval_episodes, k_eval_episodes) against the composition of existing launches:
+set_state + observe + uavenv_step_policy (eps = -1: always greedy) with SKIP_DONE until every agent is done.  Records, and the
+trajectory, must agree bit for bit."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from dqn_based_uav_3d_path_planer_amd import _lib
+from dqn_based_uav_3d_path_planer_amd import evaluate as ev
+from dqn_based_uav_3d_path_planer_amd.data import make_city26_env
+from dqn_based_uav_3d_path_planer_amd.learner import FusedDQNLearner
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+PARAM = {"w": "100", "hiden_dim": "64", "output": "3", "LEARNING_RATE": "0.001", "gamma": "0.99", "Update_loop": "3"}
+
+
+def _learner(kind, seed, straight=False):
+    torch.manual_seed(seed)
+    net = "VAnet2" if kind == "dueling" else "Qnet2"
+    L = FusedDQNLearner(dict(PARAM, NetWork=net), kind, device=DEV)
+    if straight:                                    # fc2's bias favours the middle action (steer 0): "fly straight"
+        with torch.no_grad():
+            L.q_local.fc2.bias.copy_(torch.tensor([0.0, 5.0, 0.0], device=DEV))
+    return L
+
+
+def _hand_rows(K):
+    """Rows that reach the rare branches: an empty list, the final sub-goal within reach, the goal within 7 m of a UAV that
+    is still >= 7 m from its sub-goal.  Flown at z = 90 (above every roof of the stock world)."""
+    sg = np.zeros((3, 6)); sub = np.zeros((3, K, 3)); ns = np.zeros(3, np.int32)
+    sg[0] = [100, 100, 90, 300, 300, 90]; ns[0] = 0
+    sg[1] = [100, 100, 90, 300, 300, 90]; sub[1, 0] = [100, 100, 90]; sub[1, 1] = [101, 100, 90]; ns[1] = 2
+    sg[2] = [244, 250, 90, 250, 250, 90]; sub[2, 0] = [253, 250, 90]; ns[2] = 1
+    return sg, sub, ns
+
+
+_SCN = {}
+
+
+def _scenarios(env):
+    """The env's packaged bank + held-out planner rows + the hand-built rows (device tensors)."""
+    if "s" not in _SCN:
+        sg0, sub0, ns0 = env.bank_read(0, 1024)
+        hsg, hsub, hns = ev.held_out_scenarios(env, 1024, seed=0xE7A1)
+        a, b, c = _hand_rows(env.K)
+        sg = np.concatenate([a, sg0, hsg.cpu().numpy()])
+        sub = np.concatenate([b, sub0, hsub.cpu().numpy()])
+        ns = np.concatenate([c, ns0, hns.cpu().numpy()]).astype(np.int32)
+        _SCN["s"] = (torch.tensor(sg, device=DEV), torch.tensor(sub, device=DEV), torch.tensor(ns, device=DEV))
+    return _SCN["s"]
+
+
+def _v0(n, seed):
+    t = np.random.default_rng(seed).uniform(0, 2 * np.pi, n)
+    return np.stack([np.cos(t), np.sin(t)], 1)      # Max_V = 1
+
+
+def _compose(L, scn, rows, v0, max_steps):
+    """The same episodes through the existing launches: one agent per episode in a fresh env with the same uav_per_env."""
+    n = len(rows)
+    sg, sub, ns = (x.cpu().numpy() for x in scn)
+    env2 = make_city26_env(n, obs_dtype="packed")
+    kin = np.concatenate([sg[rows, :3], v0, sg[rows, 3:]], 1)
+    nsub = ns[rows]
+    env2.set_state(0, kin, np.zeros(n, np.int32), nsub, sub[rows], alias=(nsub >= 2).astype(np.int32))
+    obs = [env2.observe(), env2.new_obs()]
+    act = torch.zeros(n, dtype=torch.int32, device=DEV)
+    r64 = torch.zeros(n, dtype=torch.float64, device=DEV)
+    en = torch.zeros(n, dtype=torch.float64, device=DEV)
+    info = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    adone = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    valid = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    st = env2.get_state(0, n)
+    final = st.copy()
+    ret, energy = np.zeros(n), np.zeros(n)
+    steps, coll = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    outcome = np.zeros(n, np.int64)
+    pos, acts = [st[:, :3].copy()], []
+    cap = nsub.astype(np.int64) * env2.cfg.max_step + 1
+    t = 0
+    while (outcome == 0).any():
+        rc = env2.lib.uavenv_step_policy(env2._h, C.byref(L.net), obs[t % 2].data_ptr(), -1.0, 5, t, act.data_ptr(),
+                                         obs[(t + 1) % 2].data_ptr(), r64.data_ptr(), None, None, adone.data_ptr(),
+                                         info.data_ptr(), valid.data_ptr(), en.data_ptr(), None, _lib.STEP_SKIP_DONE,
+                                         env2._stream())
+        _lib.check(rc, "uavenv_step_policy")
+        nst = env2.get_state(0, n)
+        v = (valid.cpu().numpy() == 1) & (outcome == 0)        # (a truncated agent flies on here; its episode has ended)
+        ret[v] += r64.cpu().numpy()[v]
+        energy[v] += en.cpu().numpy()[v]
+        steps[v] += 1
+        same = (nst[:, 0] == st[:, 0]) & (nst[:, 1] == st[:, 1]) & (nst[:, 2] == st[:, 2])
+        coll[v & same & (st[:, 11] > 0)] += 1                    # a moved step whose position did not change
+        a = act.cpu().numpy().copy()
+        a[~v] = -1
+        acts.append(a)
+        p = nst[:, :3].copy()
+        p[~v] = np.nan
+        pos.append(p)
+        inf = info.cpu().numpy()
+        d = v & (adone.cpu().numpy() == 1)
+        outcome[d] = np.where(inf[d] == _lib.INFO_LOSE, _lib.EVAL_LOSE, _lib.EVAL_SUCCESS)
+        tr = v & (outcome == 0) & (((max_steps > 0) & (steps >= max_steps)) | (steps >= cap))
+        outcome[tr] = _lib.EVAL_TRUNCATED
+        final[v] = nst[v]
+        st = nst
+        t += 1
+        assert t < 20000, "the composition did not finish"
+    env2.close()
+    return dict(ret=ret, energy=energy, steps=steps, coll=coll, outcome=outcome, state=final, nsub=nsub,
+                pos=np.stack(pos, 1), act=np.stack(acts, 1))
+
+
+def _check_equal(rec, res, ref, v0, T):
+    n = len(rec)
+    assert (rec["outcome"] == ref["outcome"]).all()
+    assert (rec["steps"] == ref["steps"]).all()
+    assert np.array_equal(rec["ret"], ref["ret"])
+    assert np.array_equal(rec["energy"], ref["energy"])
+    assert (rec["collisions"] == ref["coll"]).all()
+    assert (rec["subgoals"] == ref["nsub"] - ref["state"][:, 11]).all()
+    assert np.array_equal(rec["total_score"], ref["state"][:, 13])
+    assert np.array_equal(rec["path_len"], ref["state"][:, 14])
+    assert (rec["reach_goal"] == ref["state"][:, 15]).all()
+    assert np.array_equal(rec["v0x"], v0[:, 0]) and np.array_equal(rec["v0y"], v0[:, 1])
+    pos = res.positions.cpu().numpy()
+    act = res.actions.cpu().numpy().astype(np.int64)
+    k = min(T + 1, ref["pos"].shape[1])
+    assert np.array_equal(pos[:, :k], ref["pos"][:, :k], equal_nan=True)
+    assert np.array_equal(act[:, :k - 1], ref["act"][:, :k - 1])
+
+
+NETS = [("dqn", 11, False), ("dueling", 12, False), ("dqn", 13, True)]
+
+
+@pytest.mark.parametrize("kind,seed,straight", NETS)
+def test_equals_the_composed_launches(kind, seed, straight):
+    env = make_city26_env(64, obs_dtype="packed")
+    scn = _scenarios(env)
+    L = _learner(kind, seed, straight)
+    n, T, cap = 4096, 600, 600
+    m = scn[0].shape[0]
+    first = 0
+    rows = (first + np.arange(n)) % m
+    v0 = _v0(n, seed)
+    res = ev.evaluate_policy(env, L, n, scenarios=scn, first=first, v0=v0, max_steps=cap, trajectory_steps=T)
+    rec = res.host_records()
+    ref = _compose(L, scn, rows, v0, cap)
+    _check_equal(rec, res, ref, v0, T)
+    # every branch of the episode's end shows up in this set
+    assert (rec["outcome"] == _lib.EVAL_SUCCESS).any() and (rec["outcome"] == _lib.EVAL_LOSE).any()
+    assert rec["collisions"].sum() > 0
+    assert rec["outcome"][0] == _lib.EVAL_SUCCESS and rec["steps"][0] == 1 and rec["reach_goal"][0] == 0    # empty list
+    assert rec["outcome"][1] == _lib.EVAL_SUCCESS and rec["reach_goal"][1] == 1 and rec["subgoals"][1] == 2  # final sub-goal
+    assert rec["outcome"][2] == _lib.EVAL_SUCCESS and rec["reach_goal"][2] == 1 and rec["subgoals"][2] == 0  # goal within 7 m
+    env.close()
+
+
+def test_natural_completion_and_truncation():
+    env = make_city26_env(64, obs_dtype="packed")
+    scn = _scenarios(env)
+    L = _learner("dqn", 21, True)
+    for n, cap, first in ((256, 0, 3), (512, 40, 700)):
+        m = scn[0].shape[0]
+        rows = (first + np.arange(n)) % m
+        v0 = _v0(n, n)
+        T = 64
+        res = ev.evaluate_policy(env, L, n, scenarios=scn, first=first, v0=v0, max_steps=cap, trajectory_steps=T)
+        rec = res.host_records()
+        ref = _compose(L, scn, rows, v0, cap)
+        _check_equal(rec, res, ref, v0, T)
+        if cap:
+            assert (rec["outcome"] == _lib.EVAL_TRUNCATED).any()
+        else:
+            assert not (rec["outcome"] == _lib.EVAL_TRUNCATED).any()
+    env.close()
+
+
+def test_placement_invariance_and_repeatability():
+    env = make_city26_env(64, obs_dtype="packed")
+    L = _learner("dueling", 31)
+    n = 3000 + 37                                  # not a multiple of 64
+    outs = []
+    for mw in (1, 3, 0, 0):
+        res = ev.evaluate_policy(env, L, n, seed=9, max_steps=300, max_workgroups=mw)
+        outs.append(res.records.cpu().numpy().tobytes())
+    assert outs[0] == outs[1] == outs[2] == outs[3]
+    rec = np.frombuffer(outs[0], dtype=ev.RECORD_DTYPE)
+    assert (rec["steps"] > 0).all()
+    env.close()
+
+
+def test_invalid_rows_are_recorded_not_flown():
+    env = make_city26_env(64, obs_dtype="packed")
+    L = _learner("dqn", 41)
+    sg, sub, ns = (x.clone() for x in _scenarios(env))
+    ns[5] = -3
+    ns[6] = env.K + 1
+    res = ev.evaluate_policy(env, L, 16, scenarios=(sg, sub, ns), v0=_v0(16, 1))
+    rec = res.host_records()
+    assert (rec["outcome"][[5, 6]] == _lib.EVAL_INVALID).all() and (rec["steps"][[5, 6]] == 0).all()
+    assert ((rec["outcome"] != _lib.EVAL_INVALID).sum() == 14)
+    env.close()
+
+
+def test_eps_one_is_uniform_and_default_headings_are_uniform():
+    from scipy import stats
+    env = make_city26_env(64, obs_dtype="packed")
+    L = _learner("dqn", 51, True)
+    res = ev.evaluate_policy(env, L, 4096, seed=3, eps=1.0, max_steps=50, trajectory_steps=50)
+    a = res.actions.cpu().numpy().reshape(-1)
+    a = a[a >= 0]
+    cnt = np.bincount(a, minlength=3)
+    assert stats.chisquare(cnt).pvalue > 1e-4
+    g = ev.evaluate_policy(env, L, 4096, seed=3, max_steps=50).host_records()
+    assert g["steps"].sum() > 0
+    # default headings: deterministic in the seed, U[0, 2 pi)
+    r1 = ev.evaluate_policy(env, L, 8192, seed=77, max_steps=1).host_records()
+    r2 = ev.evaluate_policy(env, L, 8192, seed=77, max_steps=1).host_records()
+    assert r1.tobytes() == r2.tobytes()
+    th = np.mod(np.arctan2(r1["v0y"], r1["v0x"]), 2 * np.pi)
+    assert np.allclose(np.hypot(r1["v0x"], r1["v0y"]), 1.0)
+    assert stats.kstest(th / (2 * np.pi), "uniform").pvalue > 1e-4
+    r3 = ev.evaluate_policy(env, L, 8192, seed=78, max_steps=1).host_records()
+    assert not np.array_equal(r1["v0x"], r3["v0x"])
+    env.close()
+
+
+def _state_bytes(env):
+    st, sub, al = env.get_state(0, env.N, want_sub=True)
+    return st.tobytes() + sub.tobytes() + al.tobytes()
+
+
+def test_refusals_leave_the_env_unchanged():
+    env = make_city26_env(64, obs_dtype="packed")
+    env.reset(seed=4)
+    L = _learner("dqn", 61)
+    before, tick = _state_bytes(env), env.lib.uavenv_tick(env._h)
+    rec = torch.zeros((64, 64), dtype=torch.uint8, device=DEV)
+    lib = env.lib
+
+    def call(net=None, **kw):
+        a = _lib.UavEvalArgs()
+        a.n, a.records = 64, rec.data_ptr()
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return lib.uavenv_eval_episodes(env._h, C.byref(net if net is not None else L.net), C.byref(a), env._stream())
+
+    assert call() == 0
+    torch.cuda.synchronize()
+    assert call(n=0) == _lib.EINVAL
+    assert call(first=-1) == _lib.EINVAL
+    assert call(records=rec.data_ptr() + 4) == _lib.EINVAL
+    assert call(records=None) == _lib.EINVAL
+    sg = torch.zeros((4, 6), dtype=torch.float64, device=DEV)
+    assert call(start_goal=sg.data_ptr(), m=4) == _lib.EINVAL                            # only one of the three
+    sub = torch.zeros((4, env.K, 3), dtype=torch.float64, device=DEV)
+    ns = torch.zeros(4, dtype=torch.int32, device=DEV)
+    assert call(start_goal=sg.data_ptr(), sub=sub.data_ptr(), nsub=ns.data_ptr(), m=0) == _lib.EINVAL
+    assert call(traj_steps=5) == _lib.EINVAL
+    f16 = _lib.UavDqnNet.from_buffer_copy(L.net); f16.mfma_dtype = _lib.MFMA_F16
+    assert call(net=f16) == _lib.EINVAL
+    big = _lib.UavDqnNet.from_buffer_copy(L.net); big.n_actions = 4
+    assert call(net=big) == _lib.EINVAL
+    wide = _lib.UavDqnNet.from_buffer_copy(L.net); wide.hid = 32
+    assert call(net=wide) == _lib.EINVAL
+    L5 = FusedDQNLearner(dict(PARAM, NetWork="VAnet2", output="5"), "dueling", device=DEV)
+    assert call(net=L5.net) == _lib.EINVAL                                               # 6 layer-2 outputs
+    torch.cuda.synchronize()
+    assert _state_bytes(env) == before and env.lib.uavenv_tick(env._h) == tick
+    env.close()
+    apf = make_city26_env(64, obs_dtype="packed", apf_enabled=1)
+    a = _lib.UavEvalArgs(); a.n, a.records = 64, rec.data_ptr()
+    assert apf.lib.uavenv_eval_episodes(apf._h, C.byref(L.net), C.byref(a), apf._stream()) == _lib.EINVAL
+    apf.close()
+    from dqn_based_uav_3d_path_planer_amd.env import VecPathPlanEnv
+    from dqn_based_uav_3d_path_planer_amd.data import load_city26
+    nob = VecPathPlanEnv(64, load_city26()["buildings"], obs_dtype="packed")               # no bank
+    assert nob.lib.uavenv_eval_episodes(nob._h, C.byref(L.net), C.byref(a), nob._stream()) == _lib.EINVAL
+    nob.close()
+
+
+def test_training_is_the_same_with_an_evaluation_in_between():
+    from dqn_based_uav_3d_path_planer_amd.loop import HotLoop
+    from dqn_based_uav_3d_path_planer_amd.replay import DeviceReplayRing
+
+    def run(with_eval):
+        env = make_city26_env(4096, obs_dtype="packed")
+        ring = DeviceReplayRing(env, 1 << 16, discrete=True)
+        ring.reset(seed=1000)
+        torch.manual_seed(42)
+        L = FusedDQNLearner(dict(PARAM, NetWork="Qnet2"), "dqn", device=DEV)
+        loop = HotLoop(ring, L, 1024, seed=7, eps=0.1)
+        loop.run(12)
+        if with_eval:
+            ev.evaluate_policy(env, L, 2048, seed=5, max_steps=200).summary()
+        loop.run(12)
+        torch.cuda.synchronize()
+        out = (L.flat.cpu().numpy().tobytes(), ring.obs.cpu().numpy().tobytes(), ring.action.cpu().numpy().tobytes(),
+               ring.reward.cpu().numpy().tobytes(), _state_bytes(env), env.lib.uavenv_tick(env._h))
+        env.close()
+        return out
+
+    assert run(False) == run(True)
+
+
+def test_plugin_evaluate_policy(tmp_path, monkeypatch):
+    from dqn_based_uav_3d_path_planer_amd import driver
+
+    def episode(with_eval):
+        torch.manual_seed(0)
+        d = tmp_path / ("eval" if with_eval else "plain")
+        d.mkdir()
+        monkeypatch.chdir(d)                       # (the config's paths are relative to the working directory)
+        sim = driver.simulator(driver.make_config_dir(str(d), "DuelingDQN", num_envs=64, num_uav=2))
+        env = sim.env
+        summ = None
+        if with_eval:
+            summ = env.evaluate_policy(n_episodes=128, seed=1, max_steps=300)
+            # the two slots fly the same missions from the same headings: with the same weights everything but the energy
+            # (each slot's own power parameters) is the same
+            l0, l1 = (u.Trainer.learner for u in env.Agents)
+            saved = l1.flat.clone()
+            with torch.no_grad():
+                l1.flat.copy_(l0.flat)
+            same = env.evaluate_policy(n_episodes=128, seed=1, max_steps=300)
+            with torch.no_grad():
+                l1.flat.copy_(saved)
+            for k in ("success", "lose", "truncated", "mean_return", "mean_steps", "mean_path_len", "mean_subgoals",
+                      "mean_collisions", "average_score"):
+                assert same[0][k] == same[1][k], k
+            assert same[0]["mean_energy"] != same[1]["mean_energy"]
+            assert same[0] == summ[0]
+        torch.manual_seed(1)
+        res = env.run_eposide(0.5)
+        return summ, res
+
+    summ, res1 = episode(True)
+    assert len(summ) == 2
+    for s in summ:
+        assert s["episodes"] == 128 and s["success"] + s["lose"] + s["truncated"] + s["invalid"] == 128
+    _, res0 = episode(False)
+    assert res0["success"] == res1["success"] and res0["lose"] == res1["lose"] and res0["sum_epoch"] == res1["sum_epoch"]
+    assert (res0["loss"] == res1["loss"]) or (np.isnan(res0["loss"]) and np.isnan(res1["loss"]))
+
+
+def test_oracle_replay_of_recorded_actions():
+    """The kernel's recorded actions replayed through the C oracle (oracle/uav_oracle.c, which shares no code with the device
+    step) from the same reset: positions and return to 1e-9, outcome and step count exactly."""
+    from oracle import pyoracle as po
+    from dqn_based_uav_3d_path_planer_amd.data import load_city26
+    env = make_city26_env(64, obs_dtype="packed")
+    scn = _scenarios(env)
+    L = _learner("dqn", 71, True)
+    n, T = 512, 600
+    first = 0                                      # (the hand-built rows first: successes of each kind, then bank and held-out rows)
+    v0 = _v0(n, 71)
+    res = ev.evaluate_policy(env, L, n, scenarios=scn, first=first, v0=v0, max_steps=T, trajectory_steps=T)
+    rec = res.host_records()
+    pos = res.positions.cpu().numpy()
+    act = res.actions.cpu().numpy().astype(np.int64)
+    sg, sub, ns = (x.cpu().numpy() for x in scn)
+    rows = (first + np.arange(n)) % len(sg)
+    c = load_city26()
+    world = po.OracleWorld(c["buildings"], c["len"], c["width"], c["h"])
+    params = dict(max_v=float(c["max_v"]), steering_angle=float(c["steering_angle"]), max_step=int(c["max_step"]), apf_enabled=0)
+    batch = po.OracleBatch(world, params, n)
+    for i in range(n):
+        u = batch.arr[i]
+        r = rows[i]
+        u.px, u.py, u.pz = (float(x) for x in sg[r, :3])
+        u.gx, u.gy, u.gz = (float(x) for x in sg[r, 3:])
+        u.vx, u.vy, u.vz = float(v0[i, 0]), float(v0[i, 1]), 0.0
+        u.V = batch.lib.orc_calc_v(C.byref(u))
+        u.step = u.done = u.reach_goal = u.error = 0
+        u.score = u.total_score = u.path_len = 0.0
+        u.n_sub = int(ns[r])
+        u.sub0_alias = 1 if int(ns[r]) >= 2 else 0
+        if ns[r] > 0:
+            C.memmove(C.addressof(u.sub), np.ascontiguousarray(sub[r, :ns[r]]).ctypes.data, int(ns[r]) * 24)
+    assert np.abs(pos[:, 0] - np.stack([batch.view["px"], batch.view["py"], batch.view["pz"]], 1)).max() == 0.0
+    steps = rec["steps"].astype(np.int64)
+    ret = np.zeros(n)
+    outcome = np.zeros(n, np.int64)
+    ended = np.zeros(n, bool)
+    for t in range(int(steps.max())):
+        alive = t < steps
+        a0 = np.where(alive, -1.0 + 2.0 * act[:, t].clip(0) / 2.0, 0.0)
+        r, d, info, _ = batch.step(a0, want_obs=False)
+        ret[alive] += r[alive]
+        p = np.stack([batch.view["px"], batch.view["py"], batch.view["pz"]], 1)
+        assert np.abs(p[alive] - pos[alive, t + 1]).max() <= 1e-9, t
+        # the oracle's own end of the episode: agent done (success / lose), else truncated at the cap
+        done_now = alive & ~ended & (batch.view["done"] == 1)
+        outcome[done_now] = np.where(info[done_now] == 2, _lib.EVAL_LOSE, _lib.EVAL_SUCCESS)
+        ended |= done_now
+        assert not (ended & (t + 1 < steps)).any(), "the oracle ended an episode before the kernel did"
+    outcome[~ended] = _lib.EVAL_TRUNCATED
+    assert (outcome == rec["outcome"]).all()
+    assert np.abs(ret - rec["ret"]).max() <= 1e-9
+    assert (ended == (rec["outcome"] != _lib.EVAL_TRUNCATED)).all()
+    assert (rec["outcome"] == _lib.EVAL_SUCCESS).any() and (rec["outcome"] == _lib.EVAL_LOSE).any()
+    assert (steps[rec["outcome"] == _lib.EVAL_TRUNCATED] == T).all()
+    env.close()
