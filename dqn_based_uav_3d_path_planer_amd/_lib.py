@@ -298,8 +298,13 @@ def load() -> C.CDLL:
     lib.uavenv_loop_step_times.restype = C.c_int
     lib.uavenv_loop_step_times.argtypes = [vp, vp, i32, C.POINTER(i32)]
     for _n in ("uavenv_sac_act_multi", "uavenv_sac_critic_grad_multi", "uavenv_sac_actor_grad_multi",
-               "uavenv_sac_critic_adam_multi", "uavenv_sac_actor_adam_multi"):       # (called from csrc/loop.hip; no Python caller)
+               "uavenv_sac_critic_adam_multi", "uavenv_sac_actor_adam_multi"):       # (called from csrc/loop.hip and by the kernel tests)
         getattr(lib, _n).restype = C.c_int
+    # arrays of n slots: nets / batches / Adam headers as ctypes arrays of the structures, `float *const *` as arrays of c_void_p
+    lib.uavenv_sac_critic_grad_multi.argtypes = [vp, vp, i32, f32, f32, vp, vp]
+    lib.uavenv_sac_actor_grad_multi.argtypes = [vp, vp, i32, f32, vp, vp]
+    lib.uavenv_sac_critic_adam_multi.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.uavenv_sac_actor_adam_multi.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, f32, f32, vp, i32, vp]
     lib.uavenv_randn.restype = C.c_int
     lib.uavenv_randn.argtypes = [u64, u64, i64, vp, vp]
     lib.uavenv_sac_loop_noise_floats.restype = C.c_int64
