@@ -41,7 +41,7 @@ SYMBOLS = (
     "uavenv_sac_critic_adam_multi", "uavenv_sac_actor_adam_multi",
     "uavenv_per_num_chunks", "uavenv_per_rotation", "uavenv_per_rebuild", "uavenv_per_sample", "uavenv_per_set", "uavenv_per_fill", "uavenv_per_set_f32", "uavenv_per_weights", "uavenv_per_fill_frame", "uavenv_per_rebuild_frame", "uavenv_p2p_allreduce", "uavenv_sac_partial_rows_n",
     "uavenv_sac_act", "uavenv_sac_reduce", "uavenv_sac_partial_rows", "uavenv_sac_last_error", "uavenv_sac_set_debug_buffer", "uavenv_sac_critic_grad", "uavenv_sac_critic_adam", "uavenv_sac_actor_grad",
-    "uavenv_sac_actor_adam", "uavenv_fed_aggregate", "uavenv_eval_episodes",
+    "uavenv_sac_actor_adam", "uavenv_fed_aggregate", "uavenv_eval_episodes", "uavenv_eval_episodes_sac", "uavenv_eval_noise_fill",
 )
 SAC_CRITIC_IN, SAC_ACTOR_PARAMS, SAC_CRITIC_PARAMS, SAC_ACTOR_STRIDE, SAC_CRITIC_STRIDE = 102, 6724, 10882, 6728, 21768
 
@@ -86,6 +86,19 @@ class UavEvalArgs(C.Structure):
     _fields_ = [("n", C.c_int32), ("first", C.c_int32), ("start_goal", C.c_void_p), ("sub", C.c_void_p),
                 ("nsub", C.c_void_p), ("m", C.c_int32), ("max_steps", C.c_int32), ("v0", C.c_void_p),
                 ("seed", C.c_uint64), ("eps", C.c_float), ("traj_steps", C.c_int32), ("records", C.c_void_p),
+                ("traj_pos", C.c_void_p), ("traj_act", C.c_void_p), ("max_workgroups", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+# uavenv_eval_episodes_sac (include/uavenv.h): the same records, flown by the SAC actor(s)
+EVAL_SAC_MEAN, EVAL_SAC_SAMPLE = 0, 1
+
+
+class UavSacEvalArgs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("first", C.c_int32), ("start_goal", C.c_void_p), ("sub", C.c_void_p),
+                ("nsub", C.c_void_p), ("m", C.c_int32), ("max_steps", C.c_int32), ("v0", C.c_void_p),
+                ("seed", C.c_uint64), ("actors", C.POINTER(C.c_void_p)), ("n_actors", C.c_int32),
+                ("action_bound", C.c_float), ("mode", C.c_int32), ("traj_steps", C.c_int32), ("records", C.c_void_p),
                 ("traj_pos", C.c_void_p), ("traj_act", C.c_void_p), ("max_workgroups", C.c_int32),
                 ("reserved0", C.c_int32)]
 
@@ -408,6 +421,10 @@ def load() -> C.CDLL:
     lib.uavenv_fed_aggregate.argtypes = [vp, i32, i32, f32, vp]
     lib.uavenv_eval_episodes.restype = C.c_int
     lib.uavenv_eval_episodes.argtypes = [vp, C.POINTER(UavDqnNet), C.POINTER(UavEvalArgs), vp]
+    lib.uavenv_eval_episodes_sac.restype = C.c_int
+    lib.uavenv_eval_episodes_sac.argtypes = [vp, C.POINTER(UavSacEvalArgs), vp]
+    lib.uavenv_eval_noise_fill.restype = C.c_int
+    lib.uavenv_eval_noise_fill.argtypes = [u64, i32, i32, vp, vp]
     if lib.uavenv_abi_version() != ABI_VERSION:
         raise UavEnvError(f"libuavenv ABI {lib.uavenv_abi_version()} != binding {ABI_VERSION}")
     _LIB = lib

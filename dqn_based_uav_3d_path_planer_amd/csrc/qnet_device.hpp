@@ -388,6 +388,17 @@ __device__ __forceinline__ void w_commit_split(const W1Split &S, const floatx4 (
 #pragma unroll
     for (int i = 0; i < 5; ++i) d[i] = R.v[i];
 }
+// The SAC actor's fc1 (64 x 100 f32, rows consecutive) + b1 -> the split form; 256 threads (the first 256 of the workgroup).  `flat` is the
+// actor's parameter block (fc1.w | fc1.b | fc_mu.w | fc_std.w | fc_mu.b | fc_std.b = net_view(flat, 4)).  Shared by the SAC kernels of
+// sac.hip and the evaluation kernel of uavenv.hip (k_eval_episodes_sac).
+__device__ __forceinline__ void stage_actor_split(const W1Split &S, const float *flat)
+{
+    floatx4 v[kStageIters];
+    SplitScRegs sc;
+    w_issue(v, flat);
+    w_issue_sc(sc, flat, flat + kHid * kW);
+    w_commit_split(S, v, sc);
+}
 // A staged layer 1 kept in MEMORY in the split form -- the LDS image, byte for byte (kSplitF floats) -- so that staging it is a
 // straight copy: the conversion above costs a 256-thread staging team ~1.5 k cycles in front of the barrier, as much as the split
 // forward saves a 16-agent strip.  The C loop keeps one image per net (built when a run starts, kept current by its own Adam
@@ -766,6 +777,28 @@ __device__ __forceinline__ int policy_select(floatx4 q, uint4 rn, float eps, int
         return act;
     }
     return (int)(((uint64_t)rn.y * (uint64_t)n_actions) >> 32);
+}
+
+// PolicyNetContinuous_SAC.forward after fc_mu / fc_std (BaseCNN.py:470-483, quirks included: std = tanh(softplus(.)), the log-prob
+// correction applies tanh to the already squashed action), ONE action dimension.  The forward-only kernels use it (k_sac_act, k_sac_td:
+// the four lane groups of a sample hold the same four head outputs, so group g evaluates dimension g & 1 only -- half the transcendental
+// work; the full head made k_sac_act VALU-bound once layer 1 had left the f32 matrix pipe), and so does the evaluation kernel of
+// uavenv.hip, whose actions must carry k_sac_act's bits.
+struct ActorOne {
+    float act, lp;
+};
+__device__ __forceinline__ ActorOne actor_head_one(float m, float sraw, float e)
+{
+    const float mu = tanhf(m);
+    const float sp = sraw > 20.0f ? sraw : log1pf(expf(sraw));          // F.softplus (beta 1, threshold 20)
+    const float sd = tanhf(sp);
+    const float ns = mu + sd * e;                                       // rsample()
+    const float df = ns - mu;
+    float lp = -(df * df) / (2.0f * (sd * sd)) - logf(sd) - 0.9189385332046727f;     // Normal.log_prob
+    const float act = tanhf(ns);
+    const float th = tanhf(act);
+    lp -= logf(1.0f - th * th + 1e-7f);
+    return ActorOne{act, lp};
 }
 
 }  // namespace uavq

@@ -169,15 +169,7 @@ __device__ __forceinline__ void stage_actor(float *W1s, const float *flat)
 }
 
 
-// actor fc1 (64 x 100 f32, rows consecutive) + b1 -> the split form; 256 threads (the first 256 of the workgroup)
-__device__ __forceinline__ void stage_actor_split(const W1Split &S, const float *flat)
-{
-    floatx4 v[kStageIters];
-    SplitScRegs sc;
-    w_issue(v, flat);
-    w_issue_sc(sc, flat, flat + kHid * kW);
-    w_commit_split(S, v, sc);
-}
+// (stage_actor_split -- actor fc1 + b1 into the split form -- lives in qnet_device.hpp: the evaluation kernel of uavenv.hip stages the same actor)
 
 // critic fc1 (64 x 102: input column c < 100 -> tile column c, the two action columns -> 101, 102, b1 -> 100) and fc2,
 // in two halves so that the loads of one net are in flight while another is being written: every thread's 13 + 4 + 2
@@ -457,25 +449,8 @@ __device__ __forceinline__ void actor_head(const float (&o)[4], float e0, float 
     }
 }
 
-// One action dimension of the head (the forward-only kernels: the four lane groups of a sample hold the same four head outputs, so
-// group g evaluates dimension g & 1 only -- half the transcendental work; the full head above made k_sac_act VALU-bound once
-// layer 1 had left the f32 matrix pipe).  Same arithmetic as actor_head for that dimension.
-struct ActorOne {
-    float act, lp;
-};
-__device__ __forceinline__ ActorOne actor_head_one(float m, float sraw, float e)
-{
-    const float mu = tanhf(m);
-    const float sp = sraw > 20.0f ? sraw : log1pf(expf(sraw));
-    const float sd = tanhf(sp);
-    const float ns = mu + sd * e;
-    const float df = ns - mu;
-    float lp = -(df * df) / (2.0f * (sd * sd)) - logf(sd) - 0.9189385332046727f;
-    const float act = tanhf(ns);
-    const float th = tanhf(act);
-    lp -= logf(1.0f - th * th + 1e-7f);
-    return ActorOne{act, lp};
-}
+// (actor_head_one -- one action dimension of the head, the form of the forward-only kernels -- lives in qnet_device.hpp: same arithmetic
+// as actor_head for that dimension)
 
 // the lane's packed row (+ {1, a0, a1, 0}: tile columns 100..103) into the packed-row tile; one lane per sample calls it
 __device__ __forceinline__ void ps_store(uint32_t *Ps, int row, const PRow &R, float a0, float a1)

@@ -189,6 +189,8 @@ struct UavEnv {
     int world_gen = 0, rp_world_gen = 0;
     long long rp_calls = 0, rp_rows_planned = 0;
     float *eval_img = nullptr;         // uavenv_eval_episodes: the net's layer-1 image (2 x UAVENV_DQN_IMAGE_FLOATS), allocated on first use
+    double *eval_sub = nullptr;        // uavenv_eval_episodes_sac on an APF env: [eval_sub_lanes][K][3] sub-goal lists of the resident lanes
+    int64_t eval_sub_lanes = 0;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1654,7 +1656,9 @@ struct EvalLane {
     double ret, energy, v0x, v0y;
 };
 
-__device__ __forceinline__ void eval_store_record(const EvalArgs &v, int e, const Agent &g, const EvalLane &L, int outcome, int slot)
+// (V: EvalArgs or SacEvalArgs -- the two evaluation kernels share the record, the installation and the episode's end)
+template <typename V>
+__device__ __forceinline__ void eval_store_record(const V &v, int e, const Agent &g, const EvalLane &L, int outcome, int slot)
 {
     uint4 *dst = v.rec + (size_t)e * 4;
     const unsigned long long r = (unsigned long long)__double_as_longlong(L.ret), t = (unsigned long long)__double_as_longlong(g.total);
@@ -1667,8 +1671,10 @@ __device__ __forceinline__ void eval_store_record(const EvalArgs &v, int e, cons
                         (uint32_t)outcome | ((uint32_t)(g.reach ? 1 : 0) << 8) | ((uint32_t)slot << 16));
 }
 
-// the first episode at or after L.e whose scenario row is valid: UAV.reset() into `g` (invalid rows get their record here)
-__device__ __forceinline__ void eval_install(const StepArgs &a, const EvalArgs &v, Agent &g, EvalLane &L)
+// the first episode at or after L.e whose scenario row is valid: UAV.reset() into `g` (invalid rows get their record here).
+// APF: the scenario's sub-goal list is copied into list `li` of a.st.sub (the evaluation's own workspace, one list per resident lane).
+template <bool APF = false, typename V>
+__device__ __forceinline__ void eval_install(const StepArgs &a, const V &v, Agent &g, EvalLane &L, int li = 0)
 {
     int row = 0;
     while (L.e < v.n) {
@@ -1701,7 +1707,7 @@ __device__ __forceinline__ void eval_install(const StepArgs &a, const EvalArgs &
     c.f[12] = vx;
     c.f[13] = vy;
     c.f[15] = angle_of<true>(vx, vy);
-    apply_reset<false>(a, L.e, g, c);
+    apply_reset<APF>(a, APF ? li : L.e, g, c);
     L.steps = 0;
     L.collisions = 0;
     L.cap = c.n_total * a.max_step + 1;
@@ -1817,6 +1823,168 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes(StepArgs a, EvalArgs v
                 double *p = v.traj_pos + ((size_t)L.e * (v.traj_steps + 1) + L.steps) * 3;
                 p[0] = g.o.px; p[1] = g.o.py; p[2] = g.o.pz;
                 v.traj_act[(size_t)L.e * v.traj_steps + L.steps - 1] = (int8_t)act;
+            }
+            // ---- 4. the end of the episode: record, then the next episode of this lane
+            const bool trunc = (v.max_steps > 0 && L.steps >= v.max_steps) || L.steps >= L.cap;
+            if (g.done || trunc) {
+                const int outcome = g.done ? (info == UAVENV_INFO_LOSE ? UAVENV_EVAL_LOSE : UAVENV_EVAL_SUCCESS) : UAVENV_EVAL_TRUNCATED;
+                eval_store_record(v, L.e, g, L, outcome, j);
+                L.e += v.lanes;
+                install = true;
+            }
+        }
+    }
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// SAC policy evaluation (uavenv_eval_episodes_sac): k_eval_episodes with the continuous actor as the policy, APF or not.
+// blockIdx.y = actor: the workgroups of slice y stage actor y once (stage_actor_split: fc1 + b1 into the split form; fc_mu / fc_std
+// and their biases as a [4][64] + [4] block, all through registers; the world by LDS-DMA) and fly the episodes e = y (mod n_actors),
+// lane l of the slice starting with episode y + n_actors l; a lane's next episode is e + (lanes of the whole grid).
+// The forward is k_sac_act's (csrc/sac.hip): fwd_strip_split + w2_load<4> / q_strip<4>(.., 4, 4, 0, .) per 16-row strip -- the same
+// operands in the same K positions, the same MFMA order -- then actor_head_one on the lane's own row: component 0 always, component 1
+// only where the trajectory wants it.  Nothing of the forward is live across the step but the lane's four head outputs.
+// APF: update_PathPlan is step_pre / step_post<MaskT, true, true> (Adjust_subgoal by the lane itself, adjust_subgoals_lane, whose lists
+// are bit-identical to k_apf_adjust's) on the lane's OWN [K][3] list: a.st.sub is the evaluation workspace here, not the env's lists,
+// and every index handed to apply_reset / step_post is the resident lane `li` -- they use it for list addressing only; what depends on
+// the UAV slot (power parameters, the record's slot) takes e mod U.  Non-APF episodes read the scenario row in place (g.scn >= 0).
+// ------------------------------------------------------------------------------------------------
+struct SacEvalArgs {
+    const float *actor[UAVENV_SAC_LOOP_MAX_SLOTS];   // flat parameter blocks (fc1.w | fc1.b | fc_mu.w | fc_std.w | fc_mu.b | fc_std.b)
+    const double *v0;                  // nullable [n][2]
+    uint4 *rec;                        // [n] x 64 bytes (UavEvalRecord)
+    double *traj_pos;                  // nullable [n][traj_steps + 1][3]
+    float *traj_act;                   // nullable [n][traj_steps][2]
+    uint64_t seed;
+    float bound;
+    int32_t mode, n_actors;
+    int32_t n, first, max_steps, traj_steps, lanes;  // lanes: of the whole grid = a lane's episode stride
+    int32_t img_off, w2_off, slot_off, slot_bytes;   // LDS byte offsets: fc1 split, fc_mu / fc_std (+ biases), per-wave slots
+};
+
+// The noise of UAVENV_EVAL_SAC_SAMPLE for (episode, step): both components.  ONE function for the episode kernel and for
+// k_eval_noise_fill, so that the table a test hands to the composed launches holds the kernel's own numbers.
+__device__ __forceinline__ float2 eval_sac_noise(uint64_t seed, int e, int step)
+{
+    const uint4 r = philox4x32_10(make_uint4((uint32_t)e, (uint32_t)step, 0u, 0x5ac0u), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+    const float u1 = ((float)(r.x >> 8) + 1.0f) * (1.0f / 16777216.0f);      // (0, 1]
+    const float u2 = (float)(r.y >> 8) * (1.0f / 16777216.0f);              // [0, 1)
+    const float rad = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincosf(6.283185307179586f * u2, &sn, &cs);
+    return make_float2(rad * cs, rad * sn);
+}
+
+__global__ void __launch_bounds__(256) k_eval_noise_fill(uint64_t seed, int n, int steps, float *__restrict__ out)
+{
+    const int64_t total = (int64_t)n * steps;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int e = (int)(i / steps);
+        const float2 z = eval_sac_noise(seed, e, (int)(i - (int64_t)e * steps));
+        out[2 * i] = z.x;
+        out[2 * i + 1] = z.y;
+    }
+}
+
+template <typename MaskT, bool APF>
+__global__ void __launch_bounds__(256, 1) k_eval_episodes_sac(StepArgs a, SacEvalArgs v)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int lane = (int)threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int tid = (int)threadIdx.x;
+    const int y = (int)blockIdx.y;
+    const float *actor = v.actor[y];
+    // ---- staging, once per workgroup: the world by LDS-DMA, the actor through registers
+    float *W2 = reinterpret_cast<float *>(smem + v.w2_off);        // fc_mu | fc_std: [4][64]
+    float *b2 = W2 + 4 * uavq::kHid;                                // [4]
+    const uavq::W1Split W1 = uavq::w1split_at(reinterpret_cast<float *>(smem + v.img_off));
+    if (wv >= 2) stage_copy_glds(smem, a, wv - 2, 2);               // (as k_eval_episodes: the world through wavefronts 2-3)
+    {
+        const uavq::NetDev nl = uavq::net_view(actor, 4);
+        const float w2v = nl.W2[tid];                               // 4 x 64 = one float per thread
+        const float b2v = nl.b2[tid & 3];
+        uavq::stage_actor_split(W1, actor);
+        W2[tid] = w2v;
+        if (tid < 4) b2[tid] = b2v;
+    }
+    Agent g = {};
+    EvalLane L = {};
+    const int li = ((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * 256 + tid;   // resident lane: its sub-goal list (APF)
+    L.e = y + v.n_actors * ((int)blockIdx.x * 256 + tid);             // this lane's first episode (installed at the loop's top)
+    bool install = true;
+    __syncthreads();                                                 // world and actor staged
+    const WorldLds<MaskT> w = world_view<MaskT>(smem, a);
+    unsigned char *slot = smem + v.slot_off + wv * v.slot_bytes;
+    ObsWaveLds *Q = reinterpret_cast<ObsWaveLds *>(slot);           // the observation work queue, then (same bytes) the rows
+    uint32_t *rows = reinterpret_cast<uint32_t *>(slot);
+    const int r16 = lane & 15, grp = lane >> 4;
+    for (;;) {
+        if (install) eval_install<APF>(a, v, g, L, li);              // (one call site: the installation is inlined once)
+        install = false;
+        if (__ballot(L.e < v.n) == 0ull) break;
+        const bool have = L.e < v.n;
+        // ---- 1. state_PathPlan of the current state, as a packed row in registers (as k_eval_episodes)
+        const ObsBits bits = obs_bits_queued(w, Q, g.o.px, g.o.py, g.o.pz, have);
+        const ObsScalars sc = obs_scalars(g.o, g.head);
+        uavq::PRow R;
+        ctile_mask_words(bits, R.m0, R.m1, R.m2);
+#pragma unroll
+        for (int k = 0; k < 11; ++k) R.sc[k] = sc.f[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) R.sg[k] = sc.f[11 + k];
+        if (!have) {                                                 // idle lane: a zero row, result discarded
+            R.m0 = R.m1 = R.m2 = 0u;
+#pragma unroll
+            for (int k = 0; k < 11; ++k) R.sc[k] = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) R.sg[k] = 0.0f;
+        }
+        wave_lds_sync();                                             // (the queue's last reads are done: the rows take its bytes)
+        uavq::prow_store_lds(rows + lane * kPackedDwords, R);
+        wave_lds_sync();
+        // ---- 2. fc_mu | fc_std of the 64 rows: four 16-row strips, lane 16 st + r keeps strip st
+        float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+        for (int st = 0; st < 4; ++st) {
+            uavq::PRow Rs;
+            uavq::prow_load(Rs, rows + (16 * st + r16) * kPackedDwords);
+            uavq::floatx4 h[4];
+            uavq::fwd_strip_split<false>(W1, Rs, h);
+            uavq::W2Frag<4> F;
+            uavq::w2_load<4>(F, W2, b2, 4);
+            float os[4];
+            uavq::q_strip<4>(h, F, 4, 4, 0, os);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = grp == st ? os[k] : o[k];
+        }
+        wave_lds_sync();                                             // the rows are read: the next iteration's queue may take the bytes
+        if (have) {
+            // ---- the action: get_action (SAC_Trainer.py:444-448), component 0 steers (UAV.py:414)
+            float2 z = make_float2(0.0f, 0.0f);
+            if (v.mode == UAVENV_EVAL_SAC_SAMPLE) z = eval_sac_noise(v.seed, L.e, L.steps);
+            const float act0 = uavq::actor_head_one(o[0], o[2], z.x).act * v.bound;
+            // ---- 3. update_PathPlan (UAV.py:397-513): step_agent's pieces
+            const int j = L.e % a.U;
+            const double a0 = decode_action(RawAction{__float_as_uint(act0), 0u}, UAVENV_ACT_STEER_F32, a.n_actions);
+            PreStep P;
+            step_pre(a, a0, g, P);
+            if (P.moved) g.head = angle_of<true>(g.o.vx, g.o.vy);   // :423
+            double r = 0.0;
+            int ret_done = 0, info = UAVENV_INFO_NORMAL;
+            bool head_set = false;
+            step_post<MaskT, APF, true>(a, w, APF ? li : L.e, a0, g, P, r, ret_done, info, head_set);
+            g.o.n_rem = g.n_total - g.sub_idx;
+            L.steps += 1;
+            L.ret += r;
+            L.energy += fly_power(a.pw, g.o.V, j);
+            // a move always changes x or y (|V_vector| = Max_V > 0): the position is back where it was only after :425-428
+            if (P.moved && g.o.px == P.ox && g.o.py == P.oy && g.o.pz == P.oz) L.collisions += 1;
+            if (L.steps <= v.traj_steps) {
+                double *p = v.traj_pos + ((size_t)L.e * (v.traj_steps + 1) + L.steps) * 3;
+                p[0] = g.o.px; p[1] = g.o.py; p[2] = g.o.pz;
+                const float act1 = uavq::actor_head_one(o[1], o[3], z.y).act * v.bound;
+                reinterpret_cast<float2 *>(v.traj_act)[(size_t)L.e * v.traj_steps + L.steps - 1] = make_float2(act0, act1);
             }
             // ---- 4. the end of the episode: record, then the next episode of this lane
             const bool trunc = (v.max_steps > 0 && L.steps >= v.max_steps) || L.steps >= L.cap;
@@ -2099,6 +2267,7 @@ int uavenv_destroy(UavEnv *e)
     if (e->rp_done) (void)hipEventDestroy(e->rp_done);
     if (e->rp_committed) (void)hipEventDestroy(e->rp_committed);
     (void)hipFree(e->eval_img);
+    (void)hipFree(e->eval_sub);
     delete e;
     return UAVENV_OK;
 }
@@ -2837,6 +3006,133 @@ int uavenv_eval_episodes(UavEnv *e, const UavDqnNet *net, const UavEvalArgs *arg
         return fail(UAVENV_EINVAL, "uavenv_eval_episodes: n %d + %d lanes exceeds the episode index range", u.n, v.lanes);
     if (e->mask_bytes == 4) hipLaunchKernelGGL(k_eval_episodes<uint32_t>, dim3(grid), dim3(256), lds, s, a, v);
     else hipLaunchKernelGGL(k_eval_episodes<uint64_t>, dim3(grid), dim3(256), lds, s, a, v);
+    HIP_TRY(hipGetLastError());
+    return UAVENV_OK;
+}
+
+int uavenv_eval_episodes_sac(UavEnv *e, const UavSacEvalArgs *args, void *stream)
+{
+    if (!e || !args) return fail(UAVENV_EINVAL, "null argument");
+    const UavSacEvalArgs &u = *args;
+    const bool apf = e->cfg.apf_enabled == 1;
+    if (!e->have_world) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac before uavenv_set_buildings");
+    if (u.n <= 0 || u.first < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: n %d, first %d", u.n, u.first);
+    if ((u.n_actors != 1 && u.n_actors != e->cfg.uav_per_env) || u.n_actors > UAVENV_SAC_LOOP_MAX_SLOTS || !u.actors)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: n_actors %d (1 or uav_per_env = %d, at most %d)", u.n_actors,
+                    e->cfg.uav_per_env, UAVENV_SAC_LOOP_MAX_SLOTS);
+    for (int k = 0; k < u.n_actors; ++k)
+        if (!u.actors[k] || (((uintptr_t)u.actors[k]) & 15u))
+            return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: actor %d must be a 16-byte aligned device pointer", k);
+    if (!std::isfinite(u.action_bound) || u.action_bound <= 0.0f)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: action_bound %g", (double)u.action_bound);
+    if (u.mode != UAVENV_EVAL_SAC_MEAN && u.mode != UAVENV_EVAL_SAC_SAMPLE) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: mode %d", u.mode);
+    if (!u.records || (((uintptr_t)u.records) & 15u) != 0)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: records must be a 16-byte aligned device pointer");
+    const int given = (u.start_goal ? 1 : 0) + (u.sub ? 1 : 0) + (u.nsub ? 1 : 0);
+    if (given != 0 && given != 3) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: give all three scenario arrays or none");
+    if (given == 3 && u.m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: m %d", u.m);
+    if (given == 0 && e->bank_m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: no scenarios (the env has no bank)");
+    if (u.traj_steps < 0 || u.traj_steps >= (1 << 30) || (u.traj_steps > 0 && (!u.traj_pos || !u.traj_act)))
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: traj_steps %d needs both trajectory pointers", u.traj_steps);
+    if (u.max_steps < 0 || u.max_workgroups < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: max_steps / max_workgroups < 0");
+    if ((((uintptr_t)u.start_goal) | ((uintptr_t)u.sub) | ((uintptr_t)u.v0) | ((uintptr_t)u.traj_pos)) & 7u)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: misaligned f64 array");
+    if ((((uintptr_t)u.nsub) & 3u) || (((uintptr_t)u.traj_act) & 7u)) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: misaligned nsub / traj_act");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+
+    // the env's parameters and world; the scenario set in the bank's place; nothing the step launches own
+    StepArgs a = base_args(e);
+    a.moved_word = nullptr;
+    a.meta = nullptr;
+    a.meta_a1 = nullptr;
+    a.dbg = nullptr;
+    a.block = 256;
+    if (given == 3) {
+        a.bank.start_goal = u.start_goal;
+        a.bank.sub = u.sub;
+        a.bank.nsub = u.nsub;
+        a.bank.m = u.m;
+    }
+    SacEvalArgs v;
+    memset(&v, 0, sizeof(v));
+    for (int k = 0; k < u.n_actors; ++k) v.actor[k] = u.actors[k];
+    v.v0 = u.v0;
+    v.rec = reinterpret_cast<uint4 *>(u.records);
+    v.traj_pos = u.traj_steps > 0 ? u.traj_pos : nullptr;
+    v.traj_act = u.traj_steps > 0 ? u.traj_act : nullptr;
+    v.seed = u.seed;
+    v.bound = u.action_bound;
+    v.mode = u.mode;
+    v.n_actors = u.n_actors;
+    v.n = u.n;
+    v.first = u.first;
+    v.max_steps = u.max_steps;
+    v.traj_steps = u.traj_steps;
+    v.img_off = (e->world_bytes + 15) & ~15;
+    v.w2_off = v.img_off + uavq::kSplitF * 4;
+    v.slot_off = (v.w2_off + (4 * uavq::kHid + 4) * 4 + 15) & ~15;
+    int slot = (int)sizeof(ObsWaveLds);            // the work queue, then (same bytes) the wavefront's 64 packed rows
+    if (slot < 64 * kPackedDwords * 4) slot = 64 * kPackedDwords * 4;
+    v.slot_bytes = (slot + 15) & ~15;
+    const size_t lds = (size_t)v.slot_off + 4 * (size_t)v.slot_bytes;
+    const bool m32 = e->mask_bytes == 4;
+    const void *fn = apf ? (m32 ? reinterpret_cast<const void *>(k_eval_episodes_sac<uint32_t, true>)
+                                : reinterpret_cast<const void *>(k_eval_episodes_sac<uint64_t, true>))
+                         : (m32 ? reinterpret_cast<const void *>(k_eval_episodes_sac<uint32_t, false>)
+                                : reinterpret_cast<const void *>(k_eval_episodes_sac<uint64_t, false>));
+    if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // grid.x, per actor: as many workgroups as stay resident beside the other actors', at most one per 256 of its episodes
+    const int64_t per_actor = ((int64_t)u.n + u.n_actors - 1) / u.n_actors;
+    const int want = (int)((per_actor + 255) / 256);
+    int grid = want;
+    if (u.max_workgroups > 0) {
+        grid = u.max_workgroups < want ? u.max_workgroups : want;
+    } else {
+        int per_cu = 0, cus = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
+        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device));
+        const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1) / u.n_actors;
+        if (resident < grid) grid = (int)(resident > 0 ? resident : 1);
+    }
+    if (grid < 1) grid = 1;
+    const int64_t lanes = (int64_t)grid * u.n_actors * 256;
+    // (a lane's next episode is e + lanes in 32-bit arithmetic: the last one taken must still be representable)
+    if ((int64_t)u.n + lanes > (int64_t)INT32_MAX)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: n %d + %lld lanes exceeds the episode index range", u.n, (long long)lanes);
+    v.lanes = (int32_t)lanes;
+    if (apf) {
+        // one private [K][3] list per resident lane; the env's own lists (e->st.sub) stay as they are.  (hipFree synchronises the
+        // device: an earlier evaluation still in flight has finished with the old workspace before it goes.)
+        if (e->eval_sub_lanes < lanes) {
+            (void)hipFree(e->eval_sub);
+            e->eval_sub = nullptr;
+            e->eval_sub_lanes = 0;
+            HIP_TRY(hipMalloc((void **)&e->eval_sub, (size_t)lanes * (size_t)a.K * 3 * sizeof(double)));
+            e->eval_sub_lanes = lanes;
+        }
+        a.st.sub = e->eval_sub;
+    }
+    const dim3 g3((unsigned)grid, (unsigned)u.n_actors);
+    if (apf) {
+        if (m32) hipLaunchKernelGGL((k_eval_episodes_sac<uint32_t, true>), g3, dim3(256), lds, s, a, v);
+        else hipLaunchKernelGGL((k_eval_episodes_sac<uint64_t, true>), g3, dim3(256), lds, s, a, v);
+    } else {
+        if (m32) hipLaunchKernelGGL((k_eval_episodes_sac<uint32_t, false>), g3, dim3(256), lds, s, a, v);
+        else hipLaunchKernelGGL((k_eval_episodes_sac<uint64_t, false>), g3, dim3(256), lds, s, a, v);
+    }
+    HIP_TRY(hipGetLastError());
+    return UAVENV_OK;
+}
+
+int uavenv_eval_noise_fill(uint64_t seed, int32_t n, int32_t steps, float *out_dev, void *stream)
+{
+    if (n <= 0 || steps <= 0 || (int64_t)n * steps >= (1ll << 31) || !out_dev || (((uintptr_t)out_dev) & 3u))
+        return fail(UAVENV_EINVAL, "uavenv_eval_noise_fill: n %d, steps %d, out %p", n, steps, (void *)out_dev);
+    const int64_t total = (int64_t)n * steps;
+    const int64_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_eval_noise_fill, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, seed, n,
+                       steps, out_dev);
     HIP_TRY(hipGetLastError());
     return UAVENV_OK;
 }

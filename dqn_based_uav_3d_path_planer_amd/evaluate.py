@@ -1,5 +1,5 @@
-"""Greedy policy evaluation: whole DQN episodes in one GPU launch (csrc/uavenv.hip k_eval_episodes, include/uavenv.h
-uavenv_eval_episodes).
+"""Policy evaluation: whole episodes in one GPU launch -- greedy DQN (csrc/uavenv.hip k_eval_episodes, include/uavenv.h
+uavenv_eval_episodes) and the continuous SAC actor, APF on or off (k_eval_episodes_sac, uavenv_eval_episodes_sac).
 
 The reference meant to have this (Envs/PathPlan_City.py:349-351 Evaluation_Action, :543-552 run_XML_scene / Load_Scene_FromXML)
 and acts greedily when Is_Train == 0 (Trainer/DuelingDQN_Trainer.py:90).  Episode e flies scenario row (first + e) mod m of a
@@ -52,7 +52,8 @@ def summarize(rec: np.ndarray) -> dict:
 @dataclass
 class EvalResult:
     """records: uint8 device tensor [n, 64] (UavEvalRecord); positions / actions: the optional trajectory, device tensors
-    [n, T + 1, 3] f64 (NaN past an episode's end) and [n, T] int8 (-1 past the end)."""
+    [n, T + 1, 3] f64 (NaN past an episode's end) and [n, T] int8 (-1 past the end) -- from evaluate_sac_policy the actions
+    are [n, T, 2] f32, the two components get_action returns (NaN past the end)."""
     records: object
     positions: Optional[object] = None
     actions: Optional[object] = None
@@ -134,6 +135,86 @@ def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int
     res = EvalResult(records, pos, act)
     res._keep = (v0, scenarios if scenarios is None else (sg, sub, ns))   # alive until the launch has read them
     return res
+
+
+SAC_MODES = {"mean": _lib.EVAL_SAC_MEAN, "sample": _lib.EVAL_SAC_SAMPLE}
+
+
+def evaluate_sac_policy(env, learners, n_episodes: int, *, scenarios=None, first: int = 0, seed: int = 0, mode: str = "mean",
+                        max_steps: int = 0, v0=None, trajectory_steps: int = 0, max_workgroups: int = 0) -> EvalResult:
+    """n_episodes episodes of the SAC actor(s) on env (a VecPathPlanEnv, APF on or off) in one launch (csrc/uavenv.hip
+    k_eval_episodes_sac, include/uavenv.h uavenv_eval_episodes_sac).
+
+    learners: one FusedSACLearner, or a list of env.uav_per_env of them -- episode e is then flown by learner e mod U, as UAV
+    slot e mod U.  The reference's get_action always samples (Trainer/SAC_Trainer.py:444-448), so mode is "mean" (noise 0: the
+    action of the distribution's centre) or "sample" (noise ~ N(0, 1) from Philox on `seed`; sac_noise gives the same numbers).
+    The other arguments, the records and the positions are evaluate_policy's; actions are [n, T, 2] f32.  max_workgroups
+    bounds the workgroups per learner (an APF env keeps one [K, 3] f64 sub-goal list per resident lane, 256 lanes per
+    workgroup).  Enqueued on the current stream."""
+    # every check first: nothing is read from the device or enqueued before the arguments are known to be good
+    _check_args(n_episodes, first, 0.0, max_steps, trajectory_steps, max_workgroups)
+    if mode not in SAC_MODES:
+        raise ValueError(f"mode must be one of {sorted(SAC_MODES)} (got {mode!r})")
+    m = _check_scenarios(scenarios, env.K)
+    n, T = int(n_episodes), int(trajectory_steps)
+    ls = list(learners) if isinstance(learners, (list, tuple)) else [learners]
+    if not ls or any(getattr(L, "_blocks", None) is None or getattr(L, "action_bound", None) is None for L in ls):
+        raise ValueError("evaluate_sac_policy needs fused SAC learners (FusedSACLearner)")
+    bound = float(ls[0].action_bound)
+    if not np.isfinite(bound) or bound <= 0.0 or any(float(L.action_bound) != bound for L in ls):
+        raise ValueError("the learners must share one positive, finite action_bound")
+    if v0 is not None and tuple(np.shape(v0)) != (n, 2):
+        raise ValueError(f"v0 must be [{n}, 2] (got {tuple(np.shape(v0))})")
+    if len(ls) != 1 and len(ls) != env.uav_per_env:
+        raise ValueError(f"one learner or uav_per_env = {env.uav_per_env} of them (got {len(ls)})")
+    import torch
+    dev = env.device
+    if v0 is not None:
+        v0 = torch.as_tensor(v0, dtype=torch.float64, device=dev).contiguous()
+    if scenarios is not None:
+        sg = torch.as_tensor(scenarios[0], dtype=torch.float64, device=dev).contiguous()
+        sub = torch.as_tensor(scenarios[1], dtype=torch.float64, device=dev).contiguous()
+        ns = torch.as_tensor(scenarios[2], dtype=torch.int32, device=dev).contiguous()
+    records = torch.zeros((n, _lib.EVAL_RECORD_BYTES), dtype=torch.uint8, device=dev)
+    pos = act = None
+    if T > 0:
+        pos = torch.full((n, T + 1, 3), float("nan"), dtype=torch.float64, device=dev)
+        act = torch.full((n, T, 2), float("nan"), dtype=torch.float32, device=dev)
+    a = _lib.UavSacEvalArgs()
+    a.n, a.first = n, int(first)
+    if scenarios is not None:
+        a.start_goal, a.sub, a.nsub, a.m = sg.data_ptr(), sub.data_ptr(), ns.data_ptr(), m
+    a.max_steps = int(max_steps)
+    a.v0 = None if v0 is None else v0.data_ptr()
+    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    actors = (C.c_void_p * len(ls))(*[L._blocks[0].data_ptr() for L in ls])
+    a.actors, a.n_actors = actors, len(ls)
+    a.action_bound = bound
+    a.mode = SAC_MODES[mode]
+    a.traj_steps = T
+    a.records = records.data_ptr()
+    a.traj_pos = None if pos is None else pos.data_ptr()
+    a.traj_act = None if act is None else act.data_ptr()
+    a.max_workgroups = int(max_workgroups)
+    _lib.check(env.lib.uavenv_eval_episodes_sac(env._h, C.byref(a), env._stream()), "uavenv_eval_episodes_sac")
+    res = EvalResult(records, pos, act)
+    res._keep = (v0, scenarios if scenarios is None else (sg, sub, ns), ls)   # alive until the launch has read them
+    return res
+
+
+def sac_noise(n: int, steps: int, seed: int, device="cuda:0"):
+    """[n, steps, 2] f32: the noise evaluate_sac_policy(mode="sample", seed=seed) uses for episode e, step t, component d
+    (uavenv_eval_noise_fill) -- to hand the same draws to FusedSACLearner.act_rows."""
+    if int(n) != n or n <= 0 or int(steps) != steps or steps <= 0 or int(n) * int(steps) >= 1 << 31:
+        raise ValueError(f"n and steps must be positive integers with n * steps < 2^31 (got {n!r}, {steps!r})")
+    import torch
+    dev = torch.device(device)
+    out = torch.empty((int(n), int(steps), 2), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().uavenv_eval_noise_fill(int(seed) & 0xFFFFFFFFFFFFFFFF, int(n), int(steps), out.data_ptr(), stream),
+                   "uavenv_eval_noise_fill")
+    return out
 
 
 def slot_scenarios(scenarios, uav_per_env: int, max_v: float, seed: int):

@@ -370,24 +370,30 @@ class PathPlan_City:
     def run_XML_scene(self):
         pass
 
-    def evaluate_policy(self, n_episodes: int = 1024, seed: int = 0, held_out: bool = True, max_steps: int = 0):
-        """Greedy evaluation of every UAV slot's DQN-family trainer (Trainer/DuelingDQN_Trainer.py:90, Is_Train == 0): one
-        summary dict per slot (dqn_based_uav_3d_path_planer_amd/evaluate.py).  Every slot flies the same n_episodes missions --
-        held-out rows planned now on a seed of their own, or the first rows of the reset bank -- from the same start and initial
-        heading, with its own power parameters (evaluate.slot_scenarios).  The env, its agents and the replay are left as they
-        were."""
+    def evaluate_policy(self, n_episodes: int = 1024, seed: int = 0, held_out: bool = True, max_steps: int = 0, mode: str = "mean"):
+        """Evaluation of every UAV slot's trainer: one summary dict per slot (dqn_based_uav_3d_path_planer_amd/evaluate.py).
+        DQN-family trainers act greedily (Trainer/DuelingDQN_Trainer.py:90, Is_Train == 0); fused SAC trainers fly their actor
+        with `mode` "mean" (noise 0) or "sample" (Trainer/SAC_Trainer.py:444-448 always samples), APF on or off -- all U actors
+        in ONE launch, slot j flying only its own episodes.  Every slot flies the same n_episodes missions -- held-out rows
+        planned now on a seed of their own, or the first rows of the reset bank -- from the same start and initial heading,
+        with its own power parameters (evaluate.slot_scenarios).  The env, its agents and the replay are left as they were."""
         from dqn_based_uav_3d_path_planer_amd import evaluate as _ev
+        from dqn_based_uav_3d_path_planer_amd.sac import FusedSACLearner
         if not hasattr(self.backend, "rrt_plan"):
             raise RuntimeError("evaluate_policy needs the GPU backend")
         n, U = int(n_episodes), self.num_UAV
         if n <= 0:
             raise ValueError(f"n_episodes must be positive (got {n_episodes!r})")
-        learners = []
-        for u in self.Agents:
-            learner = getattr(u.Trainer, "learner", None)
-            if getattr(learner, "net", None) is None:
-                raise RuntimeError(f"evaluate_policy: {u.name}'s trainer has no fused DQN-family learner")
-            learners.append(learner)
+        if mode not in _ev.SAC_MODES:
+            raise ValueError(f"mode must be one of {sorted(_ev.SAC_MODES)} (got {mode!r})")
+        learners = [getattr(u.Trainer, "learner", None) for u in self.Agents]
+        sac = [isinstance(L, FusedSACLearner) for L in learners]
+        if any(sac) and not all(sac):
+            raise RuntimeError("evaluate_policy: the slots mix fused SAC trainers with others")
+        if not any(sac):
+            for u, learner in zip(self.Agents, learners):
+                if getattr(learner, "net", None) is None:
+                    raise RuntimeError(f"evaluate_policy: {u.name}'s trainer has no fused DQN-family or fused SAC learner")
         if held_out:
             scn = _ev.held_out_scenarios(self.backend, n, seed=0x7E57_0000 + int(seed))
         else:
@@ -397,7 +403,12 @@ class PathPlan_City:
             d = self.backend.device
             scn = (torch.tensor(sg[rows], device=d), torch.tensor(sub[rows], device=d), torch.tensor(ns[rows], device=d))
         scn_u, v0 = _ev.slot_scenarios(scn, U, float(self.backend.cfg.max_v), seed)
-        # episode r * U + j = mission r as slot j; one evaluation per distinct learner (slots that share one reuse it)
+        # episode r * U + j = mission r as slot j
+        if all(sac):                                   # actor j flies the episodes = j (mod U), nothing else
+            rec = _ev.evaluate_sac_policy(self.backend, learners, n * U, scenarios=scn_u, v0=v0, seed=int(seed), mode=mode,
+                                          max_steps=int(max_steps)).host_records()
+            return [_ev.summarize(rec[j::U]) for j in range(U)]
+        # one evaluation per distinct learner (slots that share one reuse it)
         records = {}
         out = []
         for j, learner in enumerate(learners):

@@ -401,6 +401,12 @@ class FusedSACLearner:
         with torch.no_grad():
             return self.actor(states.to(self.device).float(), eps)[0]
 
+    def evaluate(self, env, n_episodes: int, **kw):
+        """Whole episodes of this learner's actor on `env` in one launch, the training run left as it is:
+        evaluate.evaluate_sac_policy(env, self, n_episodes, **kw) -> EvalResult."""
+        from . import evaluate as _ev
+        return _ev.evaluate_sac_policy(env, self, n_episodes, **kw)
+
     def act_rows(self, obs_packed: torch.Tensor, first_row: int, row_stride: int, count: int, act0: torch.Tensor,
                  act1: torch.Tensor, eps: torch.Tensor = None):
         """get_action for the agents whose packed rows are first_row + i * row_stride of `obs_packed` (a flat view of the

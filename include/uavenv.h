@@ -447,6 +447,58 @@ typedef struct UavEvalArgs {
 } UavEvalArgs;
 int uavenv_eval_episodes(UavEnv *env, const UavDqnNet *net, const UavEvalArgs *args, void *stream);
 
+/* ---- SAC policy evaluation: whole episodes of the continuous actor in one launch (Trainer/SAC_Trainer.py:444-448 get_action) -------
+ * uavenv_eval_episodes with the SAC actor (PolicyNetContinuous_SAC 100-64-(2+2), BaseClass/BaseCNN.py:459-483) as the policy, for APF
+ * and non-APF envs.  Episodes, scenario rows, the reset, v0 / the heading draw (Philox (seed; e, 0, 0, 0xe7a1)), the end of an episode,
+ * UavEvalRecord and traj_pos are those of uavenv_eval_episodes.  Episode e is flown by actor e mod n_actors (n_actors = 1, or
+ * uav_per_env <= UAVENV_SAC_LOOP_MAX_SLOTS: one actor per UAV slot) as UAV slot e mod uav_per_env.  Every step: state_PathPlan of the
+ * current state, the packed row through the forward of uavenv_sac_act (bit-identical head outputs), the head with the reference's
+ * quirks (std = tanh(softplus(.)), tanh applied twice), action = tanh(mu + std * eps) * action_bound in f32, steer = (double) of its
+ * component 0 as uavenv_step reads UAVENV_ACT_STEER_F32, then update_PathPlan (UAV.py:397-513) -- with Adjust_subgoal and the force
+ * term when the env has APF on.  get_action always samples (SAC has no greedy branch), so there are two modes:
+ *   UAVENV_EVAL_SAC_MEAN    eps = 0: the action uavenv_sac_act gives for a zero noise tensor;
+ *   UAVENV_EVAL_SAC_SAMPLE  eps ~ N(0, 1) per (episode, step, component): Box-Muller on the first two words of Philox keyed by
+ *                           (seed; e, step, 0, 0x5ac0) -- cosine branch = component 0, sine branch = component 1.
+ *                           uavenv_eval_noise_fill writes the same numbers to memory: out[(e * steps + t) * 2 + d].
+ * Only component 0 steers; component 1 is evaluated only for the trajectory.  traj_act: float [n][traj_steps][2], the two values
+ * uavenv_sac_act would have written to act0 / act1 (the caller pre-fills what lies past an episode's end, e.g. with NaN).
+ * APF mutates sub-goal lists, so every resident lane flies on a private [K][3] f64 list in an env-owned workspace: 24 K bytes per lane
+ * (1 152 B at K = 48; 256 lanes per workgroup, ~75 MB with one resident workgroup on each of 256 CUs -- max_workgroups bounds it),
+ * allocated on first use, grown (after a device synchronisation) when a later call needs more lanes, freed by uavenv_destroy.  The
+ * env's own lists are never touched, and as with uavenv_eval_episodes neither are its agents, tick, pending uavenv_set_step_meta or
+ * moved word.  Non-APF envs use no workspace.  A record does not depend on the grid.
+ * UAVENV_EINVAL, with nothing enqueued, for: no world; no scenarios at all; n <= 0; first < 0; n_actors other than 1 or uav_per_env
+ * (or > UAVENV_SAC_LOOP_MAX_SLOTS); actors NULL, or an actor block NULL or not 16-byte aligned; action_bound not finite or <= 0; an
+ * unknown mode; records NULL or not 16-byte aligned; traj_steps < 0 or >= 2^30, or > 0 without both trajectory pointers; f64 arrays
+ * or traj_act not 8-byte, nsub not 4-byte aligned; only some of the three scenario pointers, or all three with m <= 0; max_steps or
+ * max_workgroups < 0; n so large that n + the grid's lanes exceeds INT32_MAX. */
+#define UAVENV_EVAL_SAC_MEAN 0
+#define UAVENV_EVAL_SAC_SAMPLE 1
+typedef struct UavSacEvalArgs {
+    int32_t n, first;               /* as UavEvalArgs */
+    const double *start_goal;       /* dev, nullable (all three NULL: the env's bank) [m][6] */
+    const double *sub;              /* dev [m][K][3] */
+    const int32_t *nsub;            /* dev [m] */
+    int32_t m;
+    int32_t max_steps;              /* > 0: truncate after this many steps */
+    const double *v0;               /* dev, nullable [n][2] raw initial V_vector per episode */
+    uint64_t seed;                  /* headings (v0 NULL) and the noise of UAVENV_EVAL_SAC_SAMPLE */
+    const float *const *actors;     /* HOST array of n_actors device pointers: the actors' flat parameter blocks (16-byte aligned) */
+    int32_t n_actors;               /* 1 or uav_per_env */
+    float action_bound;             /* config/Trainer.xml <action_bound> */
+    int32_t mode;                   /* UAVENV_EVAL_SAC_MEAN | UAVENV_EVAL_SAC_SAMPLE */
+    int32_t traj_steps;             /* > 0: trajectory of the first traj_steps steps */
+    UavEvalRecord *records;         /* dev [n], 16-byte aligned */
+    double *traj_pos;               /* dev [n][traj_steps + 1][3] */
+    float *traj_act;                /* dev [n][traj_steps][2] */
+    int32_t max_workgroups;         /* per actor: 0 = as many as stay resident, at most one per 256 of its episodes; > 0: at most this many */
+    int32_t reserved0;
+} UavSacEvalArgs;
+int uavenv_eval_episodes_sac(UavEnv *env, const UavSacEvalArgs *args, void *stream);
+/* out_dev[(e * steps + t) * 2 + d], e < n, t < steps: the noise UAVENV_EVAL_SAC_SAMPLE uses for episode e, step t, component d.
+ * UAVENV_EINVAL for n <= 0, steps <= 0, n * steps >= 2^31 or a NULL / misaligned (4 bytes) pointer. */
+int uavenv_eval_noise_fill(uint64_t seed, int32_t n, int32_t steps, float *out_dev, void *stream);
+
 /* ---- multi-GPU: one-shot all-reduce of the gradient bucket over peer-mapped HBM (csrc/p2p.hip) ------------------- */
 /* One UavP2P per rank (= per GPU / process).  create -> every rank publishes its UAVENV_P2P_HANDLE_BYTES handle
  * (uavenv_p2p_handle) -> the `world` handles, in rank order, go to uavenv_p2p_connect on every rank.  Then, per update,

@@ -5,6 +5,14 @@ The settings (envs, learner batch, replay capacity, trainer, training epsilon, r
 (bench.parse()), so this measures the loop the benchmark times.  Baselines at pass 0: the untrained net (greedy) and eps = 1 (the
 uniform random policy).  Held-out rows are planned on a seed the training bank never uses.  Output: one JSON document.
     python scripts/learning_curve.py [--passes 1000000] [--every 50000] [--episodes 16384] [--out profiles/learning_curve_configs1.json]
+
+--config 3: BASELINE configs[3] as `bench.py --config 4` builds it (run_config4: 4 UAV slots x 32 768 envs, APF on with the
+velocities of default_rng(42), one fused SAC learner per slot, SACHotLoop), with a held-out evaluation of the four actors in one
+launch (uavenv_eval_episodes_sac) every --every passes, in both modes ("mean": noise 0; "sample": as get_action flies).  Every
+slot flies the same --episodes missions from the same headings (evaluate.slot_scenarios).  Baselines at pass 0: the untrained
+actors in both modes, and a uniform steer ~ U[-1, 1] per step flown through uavenv_step on a scratch env (the SAC kernel takes no
+caller-supplied actions).
+    python scripts/learning_curve.py --config 3 [--passes 40000] [--every 4000] [--episodes 4096] [--out profiles/learning_curve_configs3.json]
 """
 from __future__ import annotations
 
@@ -45,14 +53,139 @@ def evaluation(env, learner, scn, n, max_steps, eps=0.0):
                               "mean_steps", "mean_path_len", "mean_subgoals", "mean_collisions", "average_score")}
 
 
+KEYS = ("episodes", "success", "lose", "truncated", "success_rate", "lose_rate", "mean_return", "mean_steps", "mean_path_len",
+        "mean_subgoals", "mean_collisions", "average_score")
+
+
+def config4_settings():
+    """bench.py's settings for --config 4 (its argument parser)."""
+    import bench
+    argv, sys.argv = sys.argv, ["bench.py", "--config", "4"]
+    try:
+        a = bench.parse()
+    finally:
+        sys.argv = argv
+    return a
+
+
+def uniform_steer_baseline(velocities, scn_u, v0, U, max_steps, seed):
+    """The same episodes under steer ~ U[-1, 1] per step: set_state + uavenv_step(SKIP_DONE) on a scratch APF env, accounted
+    on the device -> one summary per slot."""
+    import numpy as np
+    from dqn_based_uav_3d_path_planer_amd import _lib
+    sg, sub, ns = (x.cpu().numpy() for x in scn_u)
+    n = len(sg)
+    env = make_city26_env(n // U, obs_dtype="packed", uav_per_env=U, apf_enabled=1, velocities=velocities)
+    kin = np.concatenate([sg[:, :3], v0.cpu().numpy(), sg[:, 3:]], 1)
+    env.set_state(0, kin, np.zeros(n, np.int32), ns, sub, alias=(ns >= 2).astype(np.int32))
+    d = env.device
+    out = env.alloc_out()
+    g = torch.Generator(device=d).manual_seed(seed)
+    ret = torch.zeros(n, dtype=torch.float64, device=d)
+    steps = torch.zeros(n, dtype=torch.int32, device=d)
+    coll = torch.zeros(n, dtype=torch.int32, device=d)
+    outcome = torch.zeros(n, dtype=torch.uint8, device=d)
+    cap = torch.as_tensor(ns.astype(np.int64) * env.cfg.max_step + 1, device=d)
+    if max_steps > 0:
+        cap = torch.clamp(cap, max=max_steps)
+    t = 0
+    while True:
+        a = torch.rand(n, device=d, generator=g, dtype=torch.float32) * 2 - 1
+        env.step(a, out, skip_done=True)
+        live = (out.valid == 1) & (outcome == 0)
+        ret += torch.where(live, out.reward, torch.zeros_like(out.reward))
+        steps += live.to(torch.int32)
+        fin = live & (out.agent_done == 1)
+        outcome[fin] = torch.where(out.info[fin] == _lib.INFO_LOSE, _lib.EVAL_LOSE, _lib.EVAL_SUCCESS).to(torch.uint8)
+        outcome[live & (outcome == 0) & (steps >= cap)] = _lib.EVAL_TRUNCATED
+        t += 1
+        if t % 16 == 0 and not bool((outcome == 0).any()):
+            break
+    st = env.get_state(0, n)
+    rec = np.zeros(n, dtype=ev.RECORD_DTYPE)
+    rec["ret"], rec["steps"], rec["outcome"] = ret.cpu().numpy(), steps.cpu().numpy(), outcome.cpu().numpy()
+    rec["total_score"], rec["path_len"], rec["subgoals"] = st[:, 13], st[:, 14], ns - st[:, 11]
+    env.close()
+    res = []
+    for j in range(U):
+        s = ev.summarize(rec[j::U])
+        res.append({k: s[k] for k in KEYS if k != "mean_collisions"})      # (collisions are not accounted on this path)
+    return res
+
+
+def main_config3(args):
+    import numpy as np
+    from dqn_based_uav_3d_path_planer_amd.loop import SACHotLoop
+    from dqn_based_uav_3d_path_planer_amd.sac import FusedSACLearner
+    b = config4_settings()
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    U, envs = 4, b.envs
+    env = make_city26_env(envs, bank="gpu", bank_size=max(envs, 4096), bank_seed=42, device=dev, obs_dtype="packed",
+                          uav_per_env=U, apf_enabled=1)
+    vel = np.random.default_rng(42).uniform(-1.0, 1.0, (len(env.buildings), 3))
+    vel[:, 2] = 0.0
+    env.set_buildings(env.buildings, velocities=vel)
+    ring = DeviceReplayRing(env, b.replay, discrete=False)
+    ring.reset(seed=1000)
+    a1_plane = torch.zeros((ring.frames, env.N), dtype=torch.float32, device=dev)
+    ring.attach_action1(a1_plane)
+    sac_param = {"actor": {"NetWork": "PolicyNetContinuous_SAC", "w": "100", "action_bound": "1", "hiden_dim": "64",
+                           "output": "2", "lr": "0.0001"},
+                 "critic": {"NetWork": "QValueNetContinuous_SAC", "w": "100", "hiden_dim": "64", "action_dim": "2", "lr": "0.001"},
+                 "SAC_param": {"IS_Continuous": "1", "alpha_lr": "0.0001", "target_entropy": "1", "gamma": "0.99", "tau": "0.05"}}
+    torch.manual_seed(42)
+    learners = [FusedSACLearner(sac_param, device=dev) for _ in range(U)]
+    loop = SACHotLoop(ring, learners, b.batch, seed=7, act1_plane=a1_plane, auto_reset=True, skip_done=True)
+    scn = ev.held_out_scenarios(env, args.episodes, seed=HELD_OUT_SEED)
+    scn_u, v0 = ev.slot_scenarios(scn, U, float(env.cfg.max_v), seed=11)
+
+    def evaluation(mode):
+        rec = ev.evaluate_sac_policy(env, learners, args.episodes * U, scenarios=scn_u, v0=v0, seed=11, mode=mode,
+                                     max_steps=args.max_steps).host_records()
+        return [{k: s[k] for k in KEYS} for s in (ev.summarize(rec[j::U]) for j in range(U))]
+
+    out = {"what": "configs[3] training (bench.py --config 4: 4 UAV slots, APF on, fused SAC, SACHotLoop) with held-out evaluations of "
+                   "the four actors in one launch; one summary per UAV slot",
+           "settings": {"envs": envs, "uav_per_env": U, "batch": b.batch, "replay": b.replay, "passes": args.passes,
+                        "every": args.every, "eval_episodes_per_slot": args.episodes, "eval_max_steps": args.max_steps,
+                        "held_out_seed": HELD_OUT_SEED},
+           "baselines": {"untrained_mean": evaluation("mean"), "untrained_sample": evaluation("sample"),
+                         "uniform_steer": uniform_steer_baseline(vel, scn_u, v0, U, args.max_steps, seed=11)},
+           "curve": []}
+    print(json.dumps({"baselines": out["baselines"]}), flush=True)
+    done, t0 = 0, time.perf_counter()
+    while done < args.passes:
+        k = min(args.every, args.passes - done)
+        loop.run(k)
+        done += k
+        row = {"pass": done, "env_steps": done * envs * U, "updates": [int(L.epoch) for L in learners],
+               "actor_loss": [float(L.loss) for L in learners], "mean": evaluation("mean"), "sample": evaluation("sample")}
+        row["wall_s"] = round(time.perf_counter() - t0, 2)
+        out["curve"].append(row)
+        print(json.dumps(row), flush=True)
+    loop.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--passes", type=int, default=1000000)
-    ap.add_argument("--every", type=int, default=50000)
-    ap.add_argument("--episodes", type=int, default=16384)
+    ap.add_argument("--config", type=int, default=1, choices=[1, 3], help="BASELINE configs[1] (DQN) or configs[3] (4 x SAC, APF)")
+    ap.add_argument("--passes", type=int, default=None)
+    ap.add_argument("--every", type=int, default=None)
+    ap.add_argument("--episodes", type=int, default=None)
     ap.add_argument("--max-steps", type=int, default=0, help="evaluation truncation (0: natural episode ends)")
-    ap.add_argument("--out", default="profiles/learning_curve_configs1.json")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    c3 = args.config == 3
+    args.passes = args.passes if args.passes is not None else (40000 if c3 else 1000000)
+    args.every = args.every if args.every is not None else (4000 if c3 else 50000)
+    args.episodes = args.episodes if args.episodes is not None else (4096 if c3 else 16384)
+    args.out = args.out or ("profiles/learning_curve_configs3.json" if c3 else "profiles/learning_curve_configs1.json")
+    if c3:
+        return main_config3(args)
     b = bench_settings()
     if b.trainer not in ("dqn", "ddqn", "dueling") or b.mfma != "f32":
         raise SystemExit("bench.py's default run is expected to be the f32 DQN family")

@@ -8,6 +8,12 @@ First the composition runs with its per-episode accounting on the device and eve
 are timed with device events, median of the repeats after a warm-up.  The composition's timed form issues exactly as many
 steps as its longest episode took, and nothing else.
     python scripts/time_eval.py [--reps 5] [--out profiles/eval_times.json]
+
+--sac: the same for SAC policy evaluation (uavenv_eval_episodes_sac; four untrained actors, one per UAV slot, mean mode) with APF
+off and on, against set_state + per step uavenv_sac_act_multi (one launch for the four slots, zero noise) + uavenv_step with
+SKIP_DONE in its default form (k_apf_adjust + k_step on the APF env).  Launches only, device events, a warm-up of both forms, then
+the two forms alternating in the same process, median of the repeats; every record checked equal before a time is taken.
+    python scripts/time_eval.py --sac [--reps 5] [--max-steps 600] [--out profiles/eval_sac_times.json]
 """
 from __future__ import annotations
 
@@ -102,12 +108,175 @@ class Composition:
         return a.elapsed_time(b)
 
 
+SAC_PARAM = {"actor": {"NetWork": "PolicyNetContinuous_SAC", "w": "100", "action_bound": "1", "hiden_dim": "64", "output": "2",
+                       "lr": "0.0001"},
+             "critic": {"NetWork": "QValueNetContinuous_SAC", "w": "100", "hiden_dim": "64", "action_dim": "2", "lr": "0.001"},
+             "SAC_param": {"IS_Continuous": "1", "alpha_lr": "0.0001", "target_entropy": "1", "gamma": "0.99", "tau": "0.05"}}
+
+
+def apf_velocities(nb):
+    """bench.py run_config4's moving cylinders (default_rng(42)), every third one static as in tests/golden/apf_episodes.npz"""
+    v = np.random.default_rng(42).uniform(-1.0, 1.0, (nb, 3))
+    v[:, 2] = 0.0
+    v[::3] = 0.0
+    return v
+
+
+class SacComposition:
+    """n agents of a fresh env (uav_per_env = U) = the n episodes; agent i is UAV slot i mod U, acted for by learner i mod U."""
+
+    def __init__(self, Ls, scn, n, v0, apf, max_steps):
+        U = len(Ls)
+        self.Ls, self.n, self.U, self.max_steps = Ls, n, U, max_steps
+        sg, sub, ns = (x.cpu().numpy() for x in scn)
+        rows = np.arange(n) % len(sg)
+        self.env = make_city26_env(n // U, obs_dtype="packed", uav_per_env=U, apf_enabled=apf)
+        if apf:
+            self.env.set_buildings(self.env.buildings, velocities=apf_velocities(len(self.env.buildings)))
+        self.kin = np.concatenate([sg[rows, :3], v0, sg[rows, 3:]], 1)
+        self.nsub = ns[rows]
+        self.sub = sub[rows]
+        d = self.env.device
+        self.obs = [self.env.new_obs(), self.env.new_obs()]
+        self.act0 = torch.zeros(n, dtype=torch.float32, device=d)
+        self.act1 = torch.zeros(n, dtype=torch.float32, device=d)
+        self.zero = torch.zeros((n // U, 2), dtype=torch.float32, device=d)
+        self.r64 = torch.zeros(n, dtype=torch.float64, device=d)
+        self.en = torch.zeros(n, dtype=torch.float64, device=d)
+        self.info = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.adone = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.valid = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.actors = (C.c_void_p * U)(*[L._blocks[0].data_ptr() for L in Ls])
+        self.eps = (C.c_void_p * U)(*[self.zero.data_ptr()] * U)
+        self.first = (C.c_int32 * U)(*range(U))
+        self.act_multi = self.env.lib.uavenv_sac_act_multi
+        self.act_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,
+                                   C.c_void_p, C.c_int32, C.c_void_p]
+
+    def reset(self):
+        self.env.set_state(0, self.kin, np.zeros(self.n, np.int32), self.nsub, self.sub, alias=(self.nsub >= 2).astype(np.int32))
+        self.env.observe(self.obs[0])
+
+    def step(self, t):
+        e, o0, o1 = self.env, self.obs[t % 2], self.obs[(t + 1) % 2]
+        rc = self.act_multi(self.actors, o0.data_ptr(), self.first, self.U, self.n // self.U, self.eps, float(self.Ls[0].action_bound),
+                            self.act0.data_ptr(), self.act1.data_ptr(), self.U, e._stream())
+        if rc != 0:
+            raise RuntimeError(f"uavenv_sac_act_multi: {rc}")
+        _lib.check(e.lib.uavenv_step(e._h, self.act0.data_ptr(), _lib.ACT_STEER_F32, o1.data_ptr(), self.r64.data_ptr(), None,
+                                     None, self.adone.data_ptr(), self.info.data_ptr(), self.valid.data_ptr(),
+                                     self.en.data_ptr(), None, _lib.STEP_SKIP_DONE, e._stream()), "uavenv_step")
+
+    def records(self):
+        """Run to the end with the per-episode accounting on the device -> (what the kernel's records must hold, steps issued)."""
+        self.reset()
+        n, d = self.n, self.env.device
+        ret = torch.zeros(n, dtype=torch.float64, device=d)
+        energy = torch.zeros(n, dtype=torch.float64, device=d)
+        steps = torch.zeros(n, dtype=torch.int32, device=d)
+        outcome = torch.zeros(n, dtype=torch.uint8, device=d)
+        total = torch.zeros(n, dtype=torch.float64, device=d)
+        cap = torch.as_tensor(self.nsub.astype(np.int64) * self.env.cfg.max_step + 1, device=d)
+        if self.max_steps > 0:
+            cap = torch.clamp(cap, max=self.max_steps)
+        t = 0
+        while True:
+            self.step(t)
+            live = (self.valid == 1) & (outcome == 0)
+            ret += torch.where(live, self.r64, torch.zeros_like(self.r64))
+            energy += torch.where(live, self.en, torch.zeros_like(self.en))
+            steps += live.to(torch.int32)
+            fin = live & (self.adone == 1)
+            outcome[fin] = torch.where(self.info[fin] == _lib.INFO_LOSE, _lib.EVAL_LOSE, _lib.EVAL_SUCCESS).to(torch.uint8)
+            outcome[live & (outcome == 0) & (steps >= cap)] = _lib.EVAL_TRUNCATED
+            t += 1
+            if t % 16 == 0 and not bool((outcome == 0).any()):
+                break
+        return dict(ret=ret.cpu().numpy(), energy=energy.cpu().numpy(), steps=steps.cpu().numpy(), outcome=outcome.cpu().numpy()), \
+            int(steps.max())
+
+    def timed(self, n_steps):
+        self.reset()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for t in range(n_steps):
+            self.step(t)
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+
+def main_sac(args):
+    from dqn_based_uav_3d_path_planer_amd.sac import FusedSACLearner
+    torch.cuda.set_device(0)
+    torch.manual_seed(0)
+    U = 4
+    Ls = [FusedSACLearner(SAC_PARAM, "cuda:0") for _ in range(U)]
+    probe = make_city26_env(64, obs_dtype="packed")
+    scn = ev.held_out_scenarios(probe, 16384, seed=0xE7A1)
+    probe.close()
+    out = {"what": "SAC policy evaluation (mean mode) of four untrained actors, one per UAV slot, on held-out city26 episodes against "
+                   "uavenv_sac_act_multi + uavenv_step (k_apf_adjust + k_step with APF on); launches only, device events, a warm-up, "
+                   "the two forms alternating, median of %d" % args.reps,
+           "max_steps": args.max_steps, "sizes": []}
+    for apf in (0, 1):
+        for n in (int(x) for x in args.sizes.split(",")):
+            v0 = np.random.default_rng(n).uniform(0, 2 * np.pi, n)
+            v0 = np.stack([np.cos(v0), np.sin(v0)], 1)
+            comp = SacComposition(Ls, scn, n, v0, apf, args.max_steps)
+            ref, n_steps = comp.records()
+            kw = dict(scenarios=scn, v0=v0, mode="mean", max_steps=args.max_steps)
+            res = ev.evaluate_sac_policy(comp.env, Ls, n, **kw)
+            rec = res.host_records()
+            ok = (np.array_equal(rec["ret"], ref["ret"]) and np.array_equal(rec["energy"], ref["energy"]) and
+                  np.array_equal(rec["steps"], ref["steps"]) and np.array_equal(rec["outcome"], ref["outcome"]))
+            if not ok:
+                raise SystemExit(f"apf {apf}, n = {n}: the kernel's records differ from the composition's; no time reported")
+            agent_steps = int(rec["steps"].sum())
+
+            def timed_eval():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                ev.evaluate_sac_policy(comp.env, Ls, n, **kw)
+                b.record()
+                b.synchronize()
+                return a.elapsed_time(b)
+
+            timed_eval()
+            comp.timed(min(n_steps, 32))
+            t_eval, t_comp = [], []
+            for _ in range(args.reps):               # the two forms alternating
+                t_eval.append(timed_eval())
+                t_comp.append(comp.timed(n_steps))
+            me, mc = float(np.median(t_eval)), float(np.median(t_comp))
+            row = {"apf": apf, "episodes": n, "agent_steps": agent_steps, "steps_longest": n_steps, "records_equal": True,
+                   "eval_ms": me, "eval_ms_all": t_eval, "comp_ms": mc, "comp_ms_all": t_comp,
+                   "comp_form": "sac_act_multi + " + ("apf_adjust + step" if apf else "step"),
+                   "eval_agent_steps_per_s": agent_steps / (me * 1e-3), "comp_agent_steps_per_s": agent_steps / (mc * 1e-3),
+                   "eval_us_per_episode": me * 1e3 / n, "comp_us_per_episode": mc * 1e3 / n, "speedup": mc / me,
+                   "summary": res.summary()}
+            print(json.dumps({k: v for k, v in row.items() if not k.endswith("_all") and k != "summary"}), flush=True)
+            out["sizes"].append(row)
+            comp.env.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="16384,65536,262144")
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default="profiles/eval_times.json")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--sac", action="store_true", help="time uavenv_eval_episodes_sac (APF off and on) instead")
+    ap.add_argument("--max-steps", type=int, default=600, help="--sac: truncate episodes (0: natural ends)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = "profiles/eval_sac_times.json" if args.sac else "profiles/eval_times.json"
+    if args.sac:
+        return main_sac(args)
     torch.cuda.set_device(0)
     torch.manual_seed(0)
     L = FusedDQNLearner(PARAM, "dqn", device="cuda:0")
