@@ -32,7 +32,7 @@ def unflatten(flat, w: int, hid: int, n2: int):
     return flat[:o_b1].reshape(hid, w), flat[o_b1:o_w2], flat[o_w2:o_b2].reshape(n2, hid), flat[o_b2:P]
 
 
-def _forward(X, W1, b1, W2, b2, dueling: bool, A: int):
+def forward_f64(X, W1, b1, W2, b2, dueling: bool, A: int):
     pre = X @ W1.T + b1
     H = np.maximum(pre, 0.0)
     out = H @ W2.T + b2
@@ -44,7 +44,7 @@ def _forward(X, W1, b1, W2, b2, dueling: bool, A: int):
     return pre, H, Q
 
 
-def _q_abs(X, W1, b1, W2, b2, dueling: bool, A: int):
+def q_abs_f64(X, W1, b1, W2, b2, dueling: bool, A: int):
     """|.|-propagated forward: a bound on the magnitude of every term a forward pass of Q sums, per sample and action."""
     habs = np.abs(X) @ np.abs(W1).T + np.abs(b1)
     oabs = habs @ np.abs(W2).T + np.abs(b2)
@@ -104,20 +104,20 @@ def dqn_grad_f64(s, s2, actions, rewards, dones, valid, local, target, *, kind: 
     Wt = unflatten(target, w, hid, n2)
     rows = np.arange(B)
 
-    pre, H, Q = _forward(X, *Wl, dueling, A)
-    _, _, Qt2 = _forward(X2, *Wt, dueling, A)
-    qabs_l = _q_abs(X, *Wl, dueling, A)
-    qabs_t = _q_abs(X2, *Wt, dueling, A)
+    pre, H, Q = forward_f64(X, *Wl, dueling, A)
+    _, _, Qt2 = forward_f64(X2, *Wt, dueling, A)
+    qabs_l = q_abs_f64(X, *Wl, dueling, A)
+    qabs_t = q_abs_f64(X2, *Wt, dueling, A)
     near = np.zeros(B, dtype=bool)
     if kind == "dqn":
         a_next = np.argmax(Qt2, axis=1)          # the value is the max whichever maximum is taken
         a_alt = a_next
     else:
-        _, _, Ql2 = _forward(X2, *Wl, dueling, A)
+        _, _, Ql2 = forward_f64(X2, *Wl, dueling, A)
         a_next = np.argmax(Ql2, axis=1)          # first maximum, as torch.max
         order = np.argsort(-Ql2, axis=1, kind="stable")
         a_alt = order[:, 1]
-        qabs_l2 = _q_abs(X2, *Wl, dueling, A)
+        qabs_l2 = q_abs_f64(X2, *Wl, dueling, A)
         gap = Ql2[rows, a_next] - Ql2[rows, a_alt]
         near = gap <= tie_eps * (qabs_l2[rows, a_next] + qabs_l2[rows, a_alt])
         if tie_eps == 0.0:

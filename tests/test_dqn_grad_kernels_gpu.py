@@ -55,6 +55,7 @@ import numpy as np
 import pytest
 import torch
 
+from dqn_fixtures import Pool, unpack
 from oracle.dqn_grad_ref import adam_step_f64, dqn_grad_f64, layout, sample_contribution
 
 pytestmark = pytest.mark.gpu
@@ -84,37 +85,6 @@ WORST = {}
 def _lib():
     from dqn_based_uav_3d_path_planer_amd import _lib as L
     return L
-
-
-class Pool:
-    """Observation rows the environment really produces (packed-representable), and a real packed ring that has wrapped."""
-
-    def __init__(self):
-        from dqn_based_uav_3d_path_planer_amd.data import make_city26_env
-        from dqn_based_uav_3d_path_planer_amd.replay import DeviceReplayRing
-        n = 2048
-        self.env = make_city26_env(n, obs_dtype="packed")
-        self.ring = DeviceReplayRing(self.env, 4 * n, discrete=True)
-        assert self.ring.frames == 5
-        self.ring.reset(seed=4)
-        gen = torch.Generator(device="cuda").manual_seed(1)
-        for _ in range(8):                                       # 8 steps on 5 frames: wrapped
-            self.ring.current_action().copy_(torch.randint(0, 3, (n,), generator=gen, device="cuda", dtype=torch.int32))
-            self.ring.step_env(auto_reset=True)
-        torch.cuda.synchronize()
-        assert self.ring.filled == 4 and self.ring.head == 3
-        self.obs = unpack(self.ring.obs)                         # [frames, n, 100] f32, exact
-        self.rows = self.obs.reshape(-1, 100)
-
-
-def unpack(obs_packed):
-    L = _lib()
-    f, n = obs_packed.shape[:2]
-    out = torch.empty((f * n, 100), dtype=torch.float32, device=obs_packed.device)
-    assert L.load().uavenv_obs_unpack(obs_packed.data_ptr(), f * n, out.data_ptr(), L.OBS_F32,
-                                      torch.cuda.current_stream().cuda_stream) == 0
-    torch.cuda.synchronize()
-    return out.view(f, n, 100).cpu().numpy()
 
 
 _POOL = None
