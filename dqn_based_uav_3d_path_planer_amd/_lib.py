@@ -41,7 +41,7 @@ SYMBOLS = (
     "uavenv_sac_critic_adam_multi", "uavenv_sac_actor_adam_multi",
     "uavenv_per_num_chunks", "uavenv_per_rotation", "uavenv_per_rebuild", "uavenv_per_sample", "uavenv_per_set", "uavenv_per_fill", "uavenv_per_set_f32", "uavenv_per_weights", "uavenv_per_fill_frame", "uavenv_per_rebuild_frame", "uavenv_p2p_allreduce", "uavenv_sac_partial_rows_n",
     "uavenv_sac_act", "uavenv_sac_reduce", "uavenv_sac_partial_rows", "uavenv_sac_last_error", "uavenv_sac_set_debug_buffer", "uavenv_sac_critic_grad", "uavenv_sac_critic_adam", "uavenv_sac_actor_grad",
-    "uavenv_sac_actor_adam", "uavenv_fed_aggregate", "uavenv_eval_episodes", "uavenv_eval_episodes_sac", "uavenv_eval_noise_fill",
+    "uavenv_sac_actor_adam", "uavenv_fed_aggregate", "uavenv_eval_episodes", "uavenv_eval_episodes_slots", "uavenv_eval_episodes_sac", "uavenv_eval_noise_fill",
 )
 SAC_CRITIC_IN, SAC_ACTOR_PARAMS, SAC_CRITIC_PARAMS, SAC_ACTOR_STRIDE, SAC_CRITIC_STRIDE = 102, 6724, 10882, 6728, 21768
 
@@ -421,6 +421,8 @@ def load() -> C.CDLL:
     lib.uavenv_fed_aggregate.argtypes = [vp, i32, i32, f32, vp]
     lib.uavenv_eval_episodes.restype = C.c_int
     lib.uavenv_eval_episodes.argtypes = [vp, C.POINTER(UavDqnNet), C.POINTER(UavEvalArgs), vp]
+    lib.uavenv_eval_episodes_slots.restype = C.c_int
+    lib.uavenv_eval_episodes_slots.argtypes = [vp, C.POINTER(C.POINTER(UavDqnNet)), i32, C.POINTER(UavEvalArgs), vp]
     lib.uavenv_eval_episodes_sac.restype = C.c_int
     lib.uavenv_eval_episodes_sac.argtypes = [vp, C.POINTER(UavSacEvalArgs), vp]
     lib.uavenv_eval_noise_fill.restype = C.c_int

@@ -189,8 +189,10 @@ struct UavEnv {
     int world_gen = 0, rp_world_gen = 0;
     long long rp_calls = 0, rp_rows_planned = 0;
     float *eval_img = nullptr;         // uavenv_eval_episodes: the net's layer-1 image (2 x UAVENV_DQN_IMAGE_FLOATS), allocated on first use
-    double *eval_sub = nullptr;        // uavenv_eval_episodes_sac on an APF env: [eval_sub_lanes][K][3] sub-goal lists of the resident lanes
+    double *eval_sub = nullptr;        // uavenv_eval_episodes_sac / _slots on an APF env: [eval_sub_lanes][K][3] sub-goal lists of the resident lanes
     int64_t eval_sub_lanes = 0;
+    float *eval_slot_img = nullptr;    // uavenv_eval_episodes_slots: eval_slot_imgs (even) layer-1 images, allocated on first use, grown on demand
+    int eval_slot_imgs = 0;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1999,6 +2001,150 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_sac(StepArgs a, SacEva
 }
 
 // ------------------------------------------------------------------------------------------------
+// Greedy DQN evaluation with one net per UAV slot, APF or not (uavenv_eval_episodes_slots): k_eval_episodes' loop with the slicing
+// and the APF step of k_eval_episodes_sac.  blockIdx.y = net: the workgroups of slice y stage net y once (its layer-1 image by
+// LDS-DMA from image y of v.img, fc2 / b2 through registers from v.local[y]; the world by LDS-DMA) and fly the episodes
+// e = y (mod n_nets), lane l of the slice starting with episode y + n_nets l; a lane's next episode is e + (lanes of the whole grid).
+// The forward, the first-maximum action, the eps draw and the heading are k_eval_episodes' (same operands in the same K positions,
+// same MFMA order: the same Q values).  APF: update_PathPlan is step_pre / step_post<MaskT, true, true> on the lane's OWN [K][3] list
+// (a.st.sub is the evaluation workspace, every index handed to apply_reset / step_post is the resident lane `li`); what depends on
+// the UAV slot (power parameters, the record's slot) takes e mod U.  Non-APF episodes read the scenario row in place.
+// ------------------------------------------------------------------------------------------------
+struct SlotsEvalArgs {
+    const float *local[UAVENV_SAC_LOOP_MAX_SLOTS];   // the nets' q_local flat blocks (fc2 / b2 are read from them)
+    const float *img;                  // n_nets layer-1 images in the split form, image y at img + y * kSplitF
+    const double *v0;                  // nullable [n][2]
+    uint4 *rec;                        // [n] x 64 bytes (UavEvalRecord)
+    double *traj_pos;                  // nullable [n][traj_steps + 1][3]
+    int8_t *traj_act;                  // nullable [n][traj_steps]
+    uint64_t seed;
+    float eps;
+    int32_t n_nets;
+    int32_t n, first, max_steps, traj_steps, lanes;  // lanes: of the whole grid = a lane's episode stride
+    int32_t n2, dueling;
+    int32_t img_off, w2_off, slot_off, slot_bytes;   // LDS byte offsets: image, fc2 (+ b2), per-wave slots
+};
+
+template <typename MaskT, bool APF>
+__global__ void __launch_bounds__(256, 1) k_eval_episodes_slots(StepArgs a, SlotsEvalArgs v)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int lane = (int)threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int tid = (int)threadIdx.x;
+    const int y = (int)blockIdx.y;
+    // ---- staging, once per workgroup: net y's image and the world by LDS-DMA, its fc2 / b2 through registers
+    float *img = reinterpret_cast<float *>(smem + v.img_off);
+    float *W2 = reinterpret_cast<float *>(smem + v.w2_off);        // [16][64]
+    float *b2 = W2 + uavq::kMaxOut * uavq::kHid;                    // [16]
+    uavq::img_glds(img, v.img + (size_t)y * uavq::kSplitF, wv);
+    if (wv >= 2) stage_copy_glds(smem, a, wv - 2, 2);               // (as k_eval_episodes: the world through wavefronts 2-3)
+    {
+        const uavq::NetDev nl = uavq::net_view(v.local[y], v.n2);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (tid + 256 * k < v.n2 * uavq::kHid) W2[tid + 256 * k] = nl.W2[tid + 256 * k];
+        if (tid < v.n2) b2[tid] = nl.b2[tid];
+    }
+    Agent g = {};
+    EvalLane L = {};
+    const int li = ((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * 256 + tid;   // resident lane: its sub-goal list (APF)
+    L.e = y + v.n_nets * ((int)blockIdx.x * 256 + tid);               // this lane's first episode (installed at the loop's top)
+    bool install = true;
+    __syncthreads();                                                 // world, image, fc2 staged
+    const WorldLds<MaskT> w = world_view<MaskT>(smem, a);
+    const uavq::W1Split W1 = uavq::w1split_at(img);
+    unsigned char *slot = smem + v.slot_off + wv * v.slot_bytes;
+    ObsWaveLds *Q = reinterpret_cast<ObsWaveLds *>(slot);           // the observation work queue, then (same bytes) the rows
+    uint32_t *rows = reinterpret_cast<uint32_t *>(slot);
+    const int r16 = lane & 15, grp = lane >> 4;
+    const int A = a.n_actions;
+    for (;;) {
+        if (install) eval_install<APF>(a, v, g, L, li);              // (one call site: the installation is inlined once)
+        install = false;
+        if (__ballot(L.e < v.n) == 0ull) break;
+        const bool have = L.e < v.n;
+        // ---- 1. state_PathPlan of the current state, as a packed row in registers (as k_eval_episodes)
+        const ObsBits bits = obs_bits_queued(w, Q, g.o.px, g.o.py, g.o.pz, have);
+        const ObsScalars sc = obs_scalars(g.o, g.head);
+        uavq::PRow R;
+        ctile_mask_words(bits, R.m0, R.m1, R.m2);
+#pragma unroll
+        for (int k = 0; k < 11; ++k) R.sc[k] = sc.f[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) R.sg[k] = sc.f[11 + k];
+        if (!have) {                                                 // idle lane: a zero row, result discarded
+            R.m0 = R.m1 = R.m2 = 0u;
+#pragma unroll
+            for (int k = 0; k < 11; ++k) R.sc[k] = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) R.sg[k] = 0.0f;
+        }
+        wave_lds_sync();                                             // (the queue's last reads are done: the rows take its bytes)
+        uavq::prow_store_lds(rows + lane * kPackedDwords, R);
+        wave_lds_sync();
+        // ---- 2. Q(s) of the 64 rows: four 16-row strips, lane 16 st + r keeps strip st (as k_eval_episodes)
+        float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+        for (int st = 0; st < 4; ++st) {
+            uavq::PRow Rs;
+            uavq::prow_load(Rs, rows + (16 * st + r16) * kPackedDwords);
+            uavq::floatx4 h[4];
+            uavq::fwd_strip_split<false>(W1, Rs, h);
+            uavq::W2Frag<4> F;
+            uavq::w2_load<4>(F, W2, b2, v.n2);
+            float qs[4];
+            uavq::q_strip<4>(h, F, v.n2, A, v.dueling, qs);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q[k] = grp == st ? qs[k] : q[k];
+        }
+        wave_lds_sync();                                             // the rows are read: the next iteration's queue may take the bytes
+        if (have) {
+            // ---- the action: k_eval_episodes' (first maximum, strict >; eps > 0: a uniform action on a draw < eps)
+            int act = 0;
+            float bq = q[0];
+#pragma unroll
+            for (int k = 1; k < 4; ++k)
+                if (k < A && q[k] > bq) { bq = q[k]; act = k; }
+            if (v.eps > 0.0f) {
+                const uint4 rn = philox4x32_10(make_uint4((uint32_t)L.e, (uint32_t)L.steps, 0u, 0xe75fu),
+                                               make_uint2((uint32_t)v.seed, (uint32_t)(v.seed >> 32)));
+                const float u = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
+                if (u < v.eps) act = (int)(((uint64_t)rn.y * (uint64_t)A) >> 32);
+            }
+            // ---- 3. update_PathPlan (UAV.py:397-513): step_agent's pieces
+            const int j = L.e % a.U;
+            const double a0 = decode_action(RawAction{(uint32_t)act, 0u}, UAVENV_ACT_INDEX_I32, A);
+            PreStep P;
+            step_pre(a, a0, g, P);
+            if (P.moved) g.head = angle_of<true>(g.o.vx, g.o.vy);   // :423
+            double r = 0.0;
+            int ret_done = 0, info = UAVENV_INFO_NORMAL;
+            bool head_set = false;
+            step_post<MaskT, APF, true>(a, w, APF ? li : L.e, a0, g, P, r, ret_done, info, head_set);
+            g.o.n_rem = g.n_total - g.sub_idx;
+            L.steps += 1;
+            L.ret += r;
+            L.energy += fly_power(a.pw, g.o.V, j);
+            // a move always changes x or y (|V_vector| = Max_V > 0): the position is back where it was only after :425-428
+            if (P.moved && g.o.px == P.ox && g.o.py == P.oy && g.o.pz == P.oz) L.collisions += 1;
+            if (L.steps <= v.traj_steps) {
+                double *p = v.traj_pos + ((size_t)L.e * (v.traj_steps + 1) + L.steps) * 3;
+                p[0] = g.o.px; p[1] = g.o.py; p[2] = g.o.pz;
+                v.traj_act[(size_t)L.e * v.traj_steps + L.steps - 1] = (int8_t)act;
+            }
+            // ---- 4. the end of the episode: record, then the next episode of this lane
+            const bool trunc = (v.max_steps > 0 && L.steps >= v.max_steps) || L.steps >= L.cap;
+            if (g.done || trunc) {
+                const int outcome = g.done ? (info == UAVENV_INFO_LOSE ? UAVENV_EVAL_LOSE : UAVENV_EVAL_SUCCESS) : UAVENV_EVAL_TRUNCATED;
+                eval_store_record(v, L.e, g, L, outcome, j);
+                L.e += v.lanes;
+                install = true;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 static bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
@@ -2268,6 +2414,7 @@ int uavenv_destroy(UavEnv *e)
     if (e->rp_committed) (void)hipEventDestroy(e->rp_committed);
     (void)hipFree(e->eval_img);
     (void)hipFree(e->eval_sub);
+    (void)hipFree(e->eval_slot_img);
     delete e;
     return UAVENV_OK;
 }
@@ -3120,6 +3267,144 @@ int uavenv_eval_episodes_sac(UavEnv *e, const UavSacEvalArgs *args, void *stream
     } else {
         if (m32) hipLaunchKernelGGL((k_eval_episodes_sac<uint32_t, false>), g3, dim3(256), lds, s, a, v);
         else hipLaunchKernelGGL((k_eval_episodes_sac<uint64_t, false>), g3, dim3(256), lds, s, a, v);
+    }
+    HIP_TRY(hipGetLastError());
+    return UAVENV_OK;
+}
+
+int uavenv_eval_episodes_slots(UavEnv *e, const UavDqnNet *const *nets, int32_t n_nets, const UavEvalArgs *args, void *stream)
+{
+    if (!e || !nets || !args) return fail(UAVENV_EINVAL, "null argument");
+    const UavEvalArgs &u = *args;
+    const bool apf = e->cfg.apf_enabled == 1;
+    if (!e->have_world) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots before uavenv_set_buildings");
+    if ((n_nets != 1 && n_nets != e->cfg.uav_per_env) || n_nets > UAVENV_SAC_LOOP_MAX_SLOTS)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: n_nets %d (1 or uav_per_env = %d, at most %d)", n_nets, e->cfg.uav_per_env,
+                    UAVENV_SAC_LOOP_MAX_SLOTS);
+    for (int k = 0; k < n_nets; ++k) {
+        const UavDqnNet *net = nets[k];
+        if (!net) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: net %d is NULL", k);
+        const int n2k = net->n_actions + (net->dueling ? 1 : 0);
+        if (!net->local || net->mfma_dtype != UAVENV_MFMA_F32 || net->w != uavq::kW || net->hid != uavq::kHid || net->n_actions < 2 ||
+            n2k > 4 || net->n_actions != e->cfg.n_actions)
+            return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: net %d: needs an f32-MFMA net of w %d, hid %d, the env's %d actions, <= 4 outputs",
+                        k, uavq::kW, uavq::kHid, e->cfg.n_actions);
+        if ((net->dueling ? 1 : 0) != (nets[0]->dueling ? 1 : 0))
+            return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: net %d differs from net 0 in dueling", k);
+        if (((uintptr_t)net->local) & 15u)
+            return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: net %d: local must be a 16-byte aligned device pointer", k);
+    }
+    const int n2 = nets[0]->n_actions + (nets[0]->dueling ? 1 : 0);
+    if (u.n <= 0 || u.first < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: n %d, first %d", u.n, u.first);
+    if (!u.records || (((uintptr_t)u.records) & 15u) != 0)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: records must be a 16-byte aligned device pointer");
+    const int given = (u.start_goal ? 1 : 0) + (u.sub ? 1 : 0) + (u.nsub ? 1 : 0);
+    if (given != 0 && given != 3) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: give all three scenario arrays or none");
+    if (given == 3 && u.m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: m %d", u.m);
+    if (given == 0 && e->bank_m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: no scenarios (the env has no bank)");
+    if (u.traj_steps < 0 || u.traj_steps >= (1 << 30) || (u.traj_steps > 0 && (!u.traj_pos || !u.traj_act)))
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: traj_steps %d needs both trajectory pointers", u.traj_steps);
+    if (u.max_steps < 0 || u.max_workgroups < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: max_steps / max_workgroups < 0");
+    if ((((uintptr_t)u.start_goal) | ((uintptr_t)u.sub) | ((uintptr_t)u.v0) | ((uintptr_t)u.traj_pos)) & 7u)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: misaligned f64 array");
+    if (((uintptr_t)u.nsub) & 3u) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: misaligned nsub");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+
+    // the env's parameters and world; the scenario set in the bank's place; nothing the step launches own
+    StepArgs a = base_args(e);
+    a.moved_word = nullptr;
+    a.meta = nullptr;
+    a.meta_a1 = nullptr;
+    a.dbg = nullptr;
+    a.block = 256;
+    if (given == 3) {
+        a.bank.start_goal = u.start_goal;
+        a.bank.sub = u.sub;
+        a.bank.nsub = u.nsub;
+        a.bank.m = u.m;
+    }
+    SlotsEvalArgs v;
+    memset(&v, 0, sizeof(v));
+    for (int k = 0; k < n_nets; ++k) v.local[k] = nets[k]->local;
+    v.v0 = u.v0;
+    v.rec = reinterpret_cast<uint4 *>(u.records);
+    v.traj_pos = u.traj_steps > 0 ? u.traj_pos : nullptr;
+    v.traj_act = u.traj_steps > 0 ? u.traj_act : nullptr;
+    v.seed = u.seed;
+    v.eps = u.eps;
+    v.n_nets = n_nets;
+    v.n = u.n;
+    v.first = u.first;
+    v.max_steps = u.max_steps;
+    v.traj_steps = u.traj_steps;
+    v.n2 = n2;
+    v.dueling = nets[0]->dueling;
+    v.img_off = (e->world_bytes + 15) & ~15;
+    v.w2_off = v.img_off + uavq::kSplitF * 4;
+    v.slot_off = (v.w2_off + (uavq::kMaxOut * uavq::kHid + uavq::kMaxOut) * 4 + 15) & ~15;
+    int slot = (int)sizeof(ObsWaveLds);            // the work queue, then (same bytes) the wavefront's 64 packed rows
+    if (slot < 64 * kPackedDwords * 4) slot = 64 * kPackedDwords * 4;
+    v.slot_bytes = (slot + 15) & ~15;
+    const size_t lds = (size_t)v.slot_off + 4 * (size_t)v.slot_bytes;
+    const bool m32 = e->mask_bytes == 4;
+    const void *fn = apf ? (m32 ? reinterpret_cast<const void *>(k_eval_episodes_slots<uint32_t, true>)
+                                : reinterpret_cast<const void *>(k_eval_episodes_slots<uint64_t, true>))
+                         : (m32 ? reinterpret_cast<const void *>(k_eval_episodes_slots<uint32_t, false>)
+                                : reinterpret_cast<const void *>(k_eval_episodes_slots<uint64_t, false>));
+    if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // grid.x, per net: as many workgroups as stay resident beside the other nets', at most one per 256 of its episodes
+    const int64_t per_net = ((int64_t)u.n + n_nets - 1) / n_nets;
+    const int want = (int)((per_net + 255) / 256);
+    int grid = want;
+    if (u.max_workgroups > 0) {
+        grid = u.max_workgroups < want ? u.max_workgroups : want;
+    } else {
+        int per_cu = 0, cus = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
+        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device));
+        const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1) / n_nets;
+        if (resident < grid) grid = (int)(resident > 0 ? resident : 1);
+    }
+    if (grid < 1) grid = 1;
+    const int64_t lanes = (int64_t)grid * n_nets * 256;
+    // (a lane's next episode is e + lanes in 32-bit arithmetic: the last one taken must still be representable)
+    if ((int64_t)u.n + lanes > (int64_t)INT32_MAX)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: n %d + %lld lanes exceeds the episode index range", u.n, (long long)lanes);
+    v.lanes = (int32_t)lanes;
+    // the nets' layer-1 images, two per image call (nets 2k and 2k + 1; the last net twice when n_nets is odd), in a buffer of this
+    // entry's own.  (hipFree synchronises the device: an earlier evaluation still in flight has finished with the old buffer.)
+    const int pairs = (n_nets + 1) / 2;
+    if (e->eval_slot_imgs < 2 * pairs) {
+        (void)hipFree(e->eval_slot_img);
+        e->eval_slot_img = nullptr;
+        e->eval_slot_imgs = 0;
+        HIP_TRY(hipMalloc((void **)&e->eval_slot_img, (size_t)(2 * pairs) * UAVENV_DQN_IMAGE_FLOATS * sizeof(float)));
+        e->eval_slot_imgs = 2 * pairs;
+    }
+    if (apf && e->eval_sub_lanes < lanes) {
+        // one private [K][3] list per resident lane, in the workspace uavenv_eval_episodes_sac uses; the env's own lists stay as they are
+        (void)hipFree(e->eval_sub);
+        e->eval_sub = nullptr;
+        e->eval_sub_lanes = 0;
+        HIP_TRY(hipMalloc((void **)&e->eval_sub, (size_t)lanes * (size_t)a.K * 3 * sizeof(double)));
+        e->eval_sub_lanes = lanes;
+    }
+    for (int k = 0; k < pairs; ++k) {
+        UavDqnNet img_net = *nets[2 * k];
+        img_net.target = nets[2 * k + 1 < n_nets ? 2 * k + 1 : 2 * k]->local;
+        const int rc = uavenv_dqn_split_image(&img_net, e->eval_slot_img + (size_t)(2 * k) * UAVENV_DQN_IMAGE_FLOATS, stream);
+        if (rc != UAVENV_OK) return fail(rc, "uavenv_eval_episodes_slots: layer-1 image");
+    }
+    v.img = e->eval_slot_img;
+    if (apf) a.st.sub = e->eval_sub;
+    const dim3 g3((unsigned)grid, (unsigned)n_nets);
+    if (apf) {
+        if (m32) hipLaunchKernelGGL((k_eval_episodes_slots<uint32_t, true>), g3, dim3(256), lds, s, a, v);
+        else hipLaunchKernelGGL((k_eval_episodes_slots<uint64_t, true>), g3, dim3(256), lds, s, a, v);
+    } else {
+        if (m32) hipLaunchKernelGGL((k_eval_episodes_slots<uint32_t, false>), g3, dim3(256), lds, s, a, v);
+        else hipLaunchKernelGGL((k_eval_episodes_slots<uint64_t, false>), g3, dim3(256), lds, s, a, v);
     }
     HIP_TRY(hipGetLastError());
     return UAVENV_OK;

@@ -1,5 +1,6 @@
 """Policy evaluation: whole episodes in one GPU launch -- greedy DQN (csrc/uavenv.hip k_eval_episodes, include/uavenv.h
-uavenv_eval_episodes) and the continuous SAC actor, APF on or off (k_eval_episodes_sac, uavenv_eval_episodes_sac).
+uavenv_eval_episodes; one net per UAV slot and APF envs: k_eval_episodes_slots, uavenv_eval_episodes_slots) and the continuous
+SAC actor, APF on or off (k_eval_episodes_sac, uavenv_eval_episodes_sac).
 
 The reference meant to have this (Envs/PathPlan_City.py:349-351 Evaluation_Action, :543-552 run_XML_scene / Load_Scene_FromXML)
 and acts greedily when Is_Train == 0 (Trainer/DuelingDQN_Trainer.py:90).  Episode e flies scenario row (first + e) mod m of a
@@ -91,7 +92,12 @@ def _check_scenarios(scenarios, K):
 
 def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int = 0, seed: int = 0, eps: float = 0.0,
                     max_steps: int = 0, v0=None, trajectory_steps: int = 0, max_workgroups: int = 0) -> EvalResult:
-    """n_episodes greedy episodes of learner.q_local (a FusedDQNLearner on the f32 MFMA) on env (a VecPathPlanEnv, APF off).
+    """n_episodes greedy episodes of learner.q_local (a FusedDQNLearner on the f32 MFMA) on env (a VecPathPlanEnv, APF on or off).
+
+    learner: one FusedDQNLearner, or a list / tuple of 1 or env.uav_per_env of them -- episode e is then flown by learner e mod U,
+    as UAV slot e mod U, all of them in ONE launch (uavenv_eval_episodes_slots; max_workgroups then bounds the workgroups per
+    learner).  A single learner on a non-APF env goes through uavenv_eval_episodes; a list, or an APF env, through the slots entry
+    (an APF env keeps one [K, 3] f64 sub-goal list per resident lane, 256 lanes per workgroup).
 
     scenarios: None (the env's bank) or (start_goal [m,6] f64, sub_goals [m,K,3] f64, n_sub [m] i32) device tensors, e.g.
     held_out_scenarios(env, m, seed).  v0: [n,2] raw initial V_vector per episode (default: headings from Philox(seed, e)).
@@ -101,10 +107,20 @@ def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int
     _check_args(n_episodes, first, eps, max_steps, trajectory_steps, max_workgroups)
     m = _check_scenarios(scenarios, env.K)
     n, T = int(n_episodes), int(trajectory_steps)
-    if getattr(learner, "net", None) is None:
-        raise ValueError("evaluate_policy needs a fused learner (FusedDQNLearner)")
+    as_list = isinstance(learner, (list, tuple))
+    ls = list(learner) if as_list else [learner]
+    if not ls or any(getattr(L, "net", None) is None for L in ls):
+        raise ValueError("evaluate_policy needs a fused learner (FusedDQNLearner), or a list of them")
+    if as_list:
+        kinds = {(getattr(L.net, "n_actions", None), getattr(L.net, "dueling", None)) for L in ls}
+        if any(k is None for kind in kinds for k in kind):
+            raise ValueError("evaluate_policy needs fused learners (FusedDQNLearner)")
+        if len(kinds) != 1:
+            raise ValueError(f"the learners must share one kind and action count (got (n_actions, dueling) = {sorted(kinds)})")
     if v0 is not None and tuple(np.shape(v0)) != (n, 2):
         raise ValueError(f"v0 must be [{n}, 2] (got {tuple(np.shape(v0))})")
+    if as_list and len(ls) != 1 and len(ls) != env.uav_per_env:
+        raise ValueError(f"one learner or uav_per_env = {env.uav_per_env} of them (got {len(ls)})")
     import torch
     dev = env.device
     if v0 is not None:
@@ -131,9 +147,13 @@ def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int
     a.traj_pos = None if pos is None else pos.data_ptr()
     a.traj_act = None if act is None else act.data_ptr()
     a.max_workgroups = int(max_workgroups)
-    _lib.check(env.lib.uavenv_eval_episodes(env._h, C.byref(learner.net), C.byref(a), env._stream()), "uavenv_eval_episodes")
+    if as_list or int(env.cfg.apf_enabled) == 1:
+        nets = (C.POINTER(_lib.UavDqnNet) * len(ls))(*[C.pointer(L.net) for L in ls])
+        _lib.check(env.lib.uavenv_eval_episodes_slots(env._h, nets, len(ls), C.byref(a), env._stream()), "uavenv_eval_episodes_slots")
+    else:
+        _lib.check(env.lib.uavenv_eval_episodes(env._h, C.byref(learner.net), C.byref(a), env._stream()), "uavenv_eval_episodes")
     res = EvalResult(records, pos, act)
-    res._keep = (v0, scenarios if scenarios is None else (sg, sub, ns))   # alive until the launch has read them
+    res._keep = (v0, scenarios if scenarios is None else (sg, sub, ns), ls)   # alive until the launch has read them
     return res
 
 

@@ -373,8 +373,9 @@ class PathPlan_City:
     def evaluate_policy(self, n_episodes: int = 1024, seed: int = 0, held_out: bool = True, max_steps: int = 0, mode: str = "mean"):
         """Evaluation of every UAV slot's trainer: one summary dict per slot (dqn_based_uav_3d_path_planer_amd/evaluate.py).
         DQN-family trainers act greedily (Trainer/DuelingDQN_Trainer.py:90, Is_Train == 0); fused SAC trainers fly their actor
-        with `mode` "mean" (noise 0) or "sample" (Trainer/SAC_Trainer.py:444-448 always samples), APF on or off -- all U actors
-        in ONE launch, slot j flying only its own episodes.  Every slot flies the same n_episodes missions -- held-out rows
+        with `mode` "mean" (noise 0) or "sample" (Trainer/SAC_Trainer.py:444-448 always samples).  APF on or off, and all U
+        nets / actors in ONE launch, slot j flying only its own episodes (DQN slots that share learners in a mixed way fall
+        back to one launch per distinct learner).  Every slot flies the same n_episodes missions -- held-out rows
         planned now on a seed of their own, or the first rows of the reset bank -- from the same start and initial heading,
         with its own power parameters (evaluate.slot_scenarios).  The env, its agents and the replay are left as they were."""
         from dqn_based_uav_3d_path_planer_amd import evaluate as _ev
@@ -408,7 +409,13 @@ class PathPlan_City:
             rec = _ev.evaluate_sac_policy(self.backend, learners, n * U, scenarios=scn_u, v0=v0, seed=int(seed), mode=mode,
                                           max_steps=int(max_steps)).host_records()
             return [_ev.summarize(rec[j::U]) for j in range(U)]
-        # one evaluation per distinct learner (slots that share one reuse it)
+        distinct = len({id(L) for L in learners})
+        if distinct == U or distinct == 1:             # net j flies the episodes = j (mod U), nothing else: ONE launch
+            who = learners if distinct == U and U > 1 else learners[0]
+            rec = _ev.evaluate_policy(self.backend, who, n * U, scenarios=scn_u, v0=v0, seed=int(seed),
+                                      max_steps=int(max_steps)).host_records()
+            return [_ev.summarize(rec[j::U]) for j in range(U)]
+        # mixed sharing: one evaluation per distinct learner (slots that share one reuse it)
         records = {}
         out = []
         for j, learner in enumerate(learners):

@@ -447,6 +447,22 @@ typedef struct UavEvalArgs {
 } UavEvalArgs;
 int uavenv_eval_episodes(UavEnv *env, const UavDqnNet *net, const UavEvalArgs *args, void *stream);
 
+/* ---- greedy DQN evaluation with one net per UAV slot, APF on or off, in one launch ---------------------------------------------------
+ * uavenv_eval_episodes for n_nets nets (n_nets = 1, or uav_per_env <= UAVENV_SAC_LOOP_MAX_SLOTS: one net per UAV slot,
+ * Envs/PathPlan_City.py:59-69) and for envs with APF on as well as off.  Episode e is flown by net e mod n_nets as UAV slot
+ * e mod uav_per_env; net j's workgroups fly only the episodes = j (mod n_nets).  Episodes, scenario rows, the reset, v0 / the heading
+ * draw, the forward, the first-maximum action, the eps draw, the end of an episode, UavEvalArgs, UavEvalRecord and the trajectory are
+ * those of uavenv_eval_episodes: with n_nets = 1 on a non-APF env the two entries write the same bytes.  With APF on, update_PathPlan
+ * runs Adjust_subgoal and the force term (UAV.py:156-210, 448-453) on a private [K][3] f64 sub-goal list per resident lane, in the
+ * env-owned workspace uavenv_eval_episodes_sac uses (24 K bytes per lane, grown on demand, freed by uavenv_destroy); the env's own
+ * lists, agents, tick, pending uavenv_set_step_meta and moved word are never touched.  max_workgroups bounds the workgroups PER NET.
+ * The nets' layer-1 images live in a buffer of this entry's own on the env (allocated on first use, grown when n_nets needs it).
+ * Calls on one env run in stream order.  A record does not depend on the grid.
+ * Takes f32-MFMA nets of w 100, hid 64, the env's n_actions >= 2 and at most 4 layer-2 outputs, all with the same `dueling`, each
+ * with a 16-byte aligned `local`.  UAVENV_EINVAL, with nothing enqueued or allocated, otherwise and for: no world; nets NULL or a NULL
+ * entry; n_nets other than 1 or uav_per_env (or > UAVENV_SAC_LOOP_MAX_SLOTS); and every argument uavenv_eval_episodes refuses. */
+int uavenv_eval_episodes_slots(UavEnv *env, const UavDqnNet *const *nets, int32_t n_nets, const UavEvalArgs *args, void *stream);
+
 /* ---- SAC policy evaluation: whole episodes of the continuous actor in one launch (Trainer/SAC_Trainer.py:444-448 get_action) -------
  * uavenv_eval_episodes with the SAC actor (PolicyNetContinuous_SAC 100-64-(2+2), BaseClass/BaseCNN.py:459-483) as the policy, for APF
  * and non-APF envs.  Episodes, scenario rows, the reset, v0 / the heading draw (Philox (seed; e, 0, 0, 0xe7a1)), the end of an episode,

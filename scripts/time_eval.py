@@ -14,6 +14,14 @@ off and on, against set_state + per step uavenv_sac_act_multi (one launch for th
 SKIP_DONE in its default form (k_apf_adjust + k_step on the APF env).  Launches only, device events, a warm-up of both forms, then
 the two forms alternating in the same process, median of the repeats; every record checked equal before a time is taken.
     python scripts/time_eval.py --sac [--reps 5] [--max-steps 600] [--out profiles/eval_sac_times.json]
+
+--slots: greedy DQN evaluation with one net per UAV slot (uavenv_eval_episodes_slots; four untrained Qnet2, U = 4), APF off and on,
+against what had to be done for the same records before that entry existed.  APF off: four uavenv_eval_episodes calls, one per net,
+each on all n episodes (every fourth record of each is kept).  APF on: set_state + per step four uavenv_dqn_act launches, each on its
+slot's rows (gathered to a contiguous block, the actions scattered back) + uavenv_step with SKIP_DONE in its default form
+(k_apf_adjust + k_step).  Launches only, device events, a warm-up of both forms, then the two forms alternating in the same process,
+median of the repeats; every record checked equal before a time is taken.
+    python scripts/time_eval.py --slots [--reps 5] [--max-steps 600] [--out profiles/eval_slots_times.json]
 """
 from __future__ import annotations
 
@@ -265,16 +273,160 @@ def main_sac(args):
         json.dump(out, f, indent=1)
 
 
+class SlotsComposition(SacComposition):
+    """SacComposition with DQN nets: per step one uavenv_dqn_act per UAV slot on that slot's rows, then uavenv_step."""
+
+    def __init__(self, Ls, scn, n, v0, apf, max_steps):
+        U = len(Ls)
+        self.Ls, self.n, self.U, self.max_steps = Ls, n, U, max_steps
+        sg, sub, ns = (x.cpu().numpy() for x in scn)
+        rows = np.arange(n) % len(sg)
+        self.env = make_city26_env(n // U, obs_dtype="packed", uav_per_env=U, apf_enabled=apf)
+        if apf:
+            self.env.set_buildings(self.env.buildings, velocities=apf_velocities(len(self.env.buildings)))
+        self.kin = np.concatenate([sg[rows, :3], v0, sg[rows, 3:]], 1)
+        self.nsub = ns[rows]
+        self.sub = sub[rows]
+        d = self.env.device
+        self.obs = [self.env.new_obs(), self.env.new_obs()]
+        self.act = torch.zeros(n, dtype=torch.int32, device=d)
+        self.rows_j = torch.zeros((n // U, self.obs[0].shape[1]), dtype=self.obs[0].dtype, device=d)
+        self.act_j = torch.zeros(n // U, dtype=torch.int32, device=d)
+        self.r64 = torch.zeros(n, dtype=torch.float64, device=d)
+        self.en = torch.zeros(n, dtype=torch.float64, device=d)
+        self.info = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.adone = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.valid = torch.zeros(n, dtype=torch.uint8, device=d)
+
+    def step(self, t):
+        e, o0, o1 = self.env, self.obs[t % 2], self.obs[(t + 1) % 2]
+        for j, L in enumerate(self.Ls):
+            self.rows_j.copy_(o0[j::self.U])
+            L.act(self.rows_j, -1.0, 5, t, index_out=self.act_j)
+            self.act[j::self.U] = self.act_j
+        _lib.check(e.lib.uavenv_step(e._h, self.act.data_ptr(), _lib.ACT_INDEX_I32, o1.data_ptr(), self.r64.data_ptr(), None,
+                                     None, self.adone.data_ptr(), self.info.data_ptr(), self.valid.data_ptr(),
+                                     self.en.data_ptr(), None, _lib.STEP_SKIP_DONE, e._stream()), "uavenv_step")
+
+
+def main_slots(args):
+    torch.cuda.set_device(0)
+    U = 4
+    Ls = []
+    for j in range(U):
+        torch.manual_seed(j)
+        Ls.append(FusedDQNLearner(PARAM, "dqn", device="cuda:0"))
+    probe = make_city26_env(64, obs_dtype="packed")
+    scn = ev.held_out_scenarios(probe, 16384, seed=0xE7A1)
+    probe.close()
+    out = {"what": "greedy evaluation of four untrained Qnet2, one per UAV slot, in one launch (uavenv_eval_episodes_slots) on held-out "
+                   "city26 episodes against what gave the same records before: APF off, four uavenv_eval_episodes calls on all the "
+                   "episodes; APF on, per step four uavenv_dqn_act (slot rows gathered, actions scattered) + uavenv_step (k_apf_adjust + "
+                   "k_step).  Launches only, device events, a warm-up, the two forms alternating, median of %d" % args.reps,
+           "max_steps": args.max_steps, "sizes": []}
+    for apf in (0, 1):
+        for n in (int(x) for x in args.sizes.split(",")):
+            v0 = np.random.default_rng(n).uniform(0, 2 * np.pi, n)
+            v0 = np.stack([np.cos(v0), np.sin(v0)], 1)
+            kw = dict(scenarios=scn, v0=v0, max_steps=args.max_steps)
+            if apf:
+                comp = SlotsComposition(Ls, scn, n, v0, apf, args.max_steps)
+                env = comp.env
+                ref, n_steps = comp.records()
+            else:
+                comp, n_steps = None, 0
+                env = make_city26_env(64, obs_dtype="packed", uav_per_env=U)
+            res = ev.evaluate_policy(env, Ls, n, **kw)
+            rec = res.host_records()
+            if apf:
+                ok = (np.array_equal(rec["ret"], ref["ret"]) and np.array_equal(rec["energy"], ref["energy"]) and
+                      np.array_equal(rec["steps"], ref["steps"]) and np.array_equal(rec["outcome"], ref["outcome"]))
+                parent_steps = agent_steps = int(rec["steps"].sum())
+            else:
+                olds = [ev.evaluate_policy(env, Ls[j], n, **kw).host_records() for j in range(U)]
+                ok = all(olds[j][j::U].tobytes() == rec[j::U].tobytes() for j in range(U))
+                parent_steps = int(sum(int(o["steps"].sum()) for o in olds))
+            if not ok:
+                raise SystemExit(f"apf {apf}, n = {n}: the one-launch records differ from the parent form's; no time reported")
+            agent_steps = int(rec["steps"].sum())
+
+            def timed(fn):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                return a.elapsed_time(b)
+
+            def one_launch():
+                ev.evaluate_policy(env, Ls, n, **kw)
+
+            def four_calls():
+                for L in Ls:
+                    ev.evaluate_policy(env, L, n, **kw)
+
+            timed(one_launch)
+            if apf:
+                comp.timed(min(n_steps, 32))
+            else:
+                timed(four_calls)
+            t_eval, t_comp = [], []
+            for _ in range(args.reps):               # the two forms alternating
+                t_eval.append(timed(one_launch))
+                t_comp.append(comp.timed(n_steps) if apf else timed(four_calls))
+            me, mc = float(np.median(t_eval)), float(np.median(t_comp))
+            row = {"apf": apf, "nets": U, "episodes": n, "agent_steps": agent_steps, "steps_longest": n_steps, "records_equal": True,
+                   "eval_ms": me, "eval_ms_all": t_eval, "comp_ms": mc, "comp_ms_all": t_comp,
+                   "comp_form": "4 x (gather + dqn_act + scatter) + apf_adjust + step" if apf else "4 x uavenv_eval_episodes on all episodes",
+                   "comp_agent_steps": parent_steps,
+                   "eval_agent_steps_per_s": agent_steps / (me * 1e-3), "eval_us_per_episode": me * 1e3 / n,
+                   "comp_us_per_episode": mc * 1e3 / n, "speedup": mc / me, "summary": res.summary()}
+            print(json.dumps({k: v for k, v in row.items() if not k.endswith("_all") and k != "summary"}), flush=True)
+            out["sizes"].append(row)
+            env.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+
+
+def main_slots_once(args):
+    """One uavenv_eval_episodes_slots launch per APF setting at `--once` episodes per net (for a kernel-trace run)."""
+    torch.cuda.set_device(0)
+    U = 4
+    Ls = []
+    for j in range(U):
+        torch.manual_seed(j)
+        Ls.append(FusedDQNLearner(PARAM, "dqn", device="cuda:0"))
+    n = args.once * U
+    probe = make_city26_env(64, obs_dtype="packed")
+    scn = ev.held_out_scenarios(probe, 16384, seed=0xE7A1)
+    probe.close()
+    for apf in (0, 1):
+        env = make_city26_env(64, obs_dtype="packed", uav_per_env=U, apf_enabled=apf)
+        if apf:
+            env.set_buildings(env.buildings, velocities=apf_velocities(len(env.buildings)))
+        v0 = np.random.default_rng(n).uniform(0, 2 * np.pi, n)
+        v0 = np.stack([np.cos(v0), np.sin(v0)], 1)
+        s = ev.evaluate_policy(env, Ls, n, scenarios=scn, v0=v0, max_steps=args.max_steps).summary()
+        print(json.dumps({"apf": apf, "episodes": n, "mean_steps": s["mean_steps"]}), flush=True)
+        env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="16384,65536,262144")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--sac", action="store_true", help="time uavenv_eval_episodes_sac (APF off and on) instead")
-    ap.add_argument("--max-steps", type=int, default=600, help="--sac: truncate episodes (0: natural ends)")
+    ap.add_argument("--max-steps", type=int, default=600, help="--sac / --slots: truncate episodes (0: natural ends)")
+    ap.add_argument("--slots", action="store_true", help="time uavenv_eval_episodes_slots (four DQN nets, APF off and on) instead")
+    ap.add_argument("--once", type=int, default=0, help="--slots: no timing, one launch per APF setting at this many episodes per net")
     args = ap.parse_args()
     if args.out is None:
-        args.out = "profiles/eval_sac_times.json" if args.sac else "profiles/eval_times.json"
+        args.out = "profiles/eval_slots_times.json" if args.slots else "profiles/eval_sac_times.json" if args.sac else "profiles/eval_times.json"
+    if args.slots:
+        return main_slots_once(args) if args.once > 0 else main_slots(args)
     if args.sac:
         return main_sac(args)
     torch.cuda.set_device(0)
