@@ -42,6 +42,8 @@ SYMBOLS = (
     "uavenv_per_num_chunks", "uavenv_per_rotation", "uavenv_per_rebuild", "uavenv_per_sample", "uavenv_per_set", "uavenv_per_fill", "uavenv_per_set_f32", "uavenv_per_weights", "uavenv_per_fill_frame", "uavenv_per_rebuild_frame", "uavenv_p2p_allreduce", "uavenv_sac_partial_rows_n",
     "uavenv_sac_act", "uavenv_sac_reduce", "uavenv_sac_partial_rows", "uavenv_sac_last_error", "uavenv_sac_set_debug_buffer", "uavenv_sac_critic_grad", "uavenv_sac_critic_adam", "uavenv_sac_actor_grad",
     "uavenv_sac_actor_adam", "uavenv_fed_aggregate", "uavenv_eval_episodes", "uavenv_eval_episodes_slots", "uavenv_eval_episodes_sac", "uavenv_eval_noise_fill",
+    "uavenv_dqn_act_slots", "uavenv_replay_draw_slots", "uavenv_dqn_slots_loop_create", "uavenv_dqn_slots_loop_destroy",
+    "uavenv_dqn_slots_loop_set_eps", "uavenv_dqn_slots_loop_run", "uavenv_dqn_slots_loop_get",
 )
 SAC_CRITIC_IN, SAC_ACTOR_PARAMS, SAC_CRITIC_PARAMS, SAC_ACTOR_STRIDE, SAC_CRITIC_STRIDE = 102, 6724, 10882, 6728, 21768
 
@@ -181,6 +183,27 @@ class UavSacLoopConfig(C.Structure):
 class UavSacLoopCursor(C.Structure):
     _fields_ = [("head", C.c_int32), ("filled", C.c_int32), ("counter", C.c_uint64),
                 ("epoch", C.c_int32 * SAC_LOOP_MAX_SLOTS), ("adam_steps", C.c_int32 * SAC_LOOP_MAX_SLOTS)]
+
+
+DQN_MAX_SLOTS = 8
+
+
+class UavDqnSlotsLoopSlot(C.Structure):
+    _fields_ = [("net", UavDqnNet), ("partials_dev", C.c_void_p), ("loss_dev", C.c_void_p), ("epoch", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+class UavDqnSlotsLoopConfig(C.Structure):
+    _fields_ = [("env", C.c_void_p), ("ring", UavReplayRing), ("info_dev", C.c_void_p), ("moved_dev", C.c_void_p),
+                ("draws_dev", C.c_void_p), ("n_slots", C.c_int32), ("batch", C.c_int32), ("head", C.c_int32), ("filled", C.c_int32),
+                ("kind", C.c_int32), ("huber", C.c_int32), ("update_loop", C.c_int32), ("learn_start", C.c_int32),
+                ("valid_draws", C.c_int32), ("step_flags", C.c_uint32), ("seed", C.c_uint64), ("counter", C.c_uint64),
+                ("eps", C.c_float), ("gamma", C.c_float), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("adam_eps", C.c_float), ("slot", UavDqnSlotsLoopSlot * DQN_MAX_SLOTS)]
+
+
+class UavDqnSlotsLoopCursor(C.Structure):
+    _fields_ = [("head", C.c_int32), ("filled", C.c_int32), ("counter", C.c_uint64), ("epoch", C.c_int32 * DQN_MAX_SLOTS)]
 
 
 class UavEnvError(RuntimeError):
@@ -427,6 +450,23 @@ def load() -> C.CDLL:
     lib.uavenv_eval_episodes_sac.argtypes = [vp, C.POINTER(UavSacEvalArgs), vp]
     lib.uavenv_eval_noise_fill.restype = C.c_int
     lib.uavenv_eval_noise_fill.argtypes = [u64, i32, i32, vp, vp]
+    lib.uavenv_dqn_act_slots.restype = C.c_int
+    lib.uavenv_dqn_act_slots.argtypes = [C.POINTER(C.POINTER(UavDqnNet)), i32, vp, i32, i32, f32, u64, u64, vp, vp, vp]
+    # (csrc/dqn_slots_internal.hpp: the form the slots loop calls, with one layer-1 image per net as an array of c_void_p)
+    lib.uavenv_dqn_act_slots_img.restype = C.c_int
+    lib.uavenv_dqn_act_slots_img.argtypes = [C.POINTER(C.POINTER(UavDqnNet)), i32, vp, i32, i32, f32, u64, u64, vp, vp, vp, vp]
+    lib.uavenv_replay_draw_slots.restype = C.c_int
+    lib.uavenv_replay_draw_slots.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32, u64, u64, vp, vp]
+    lib.uavenv_dqn_slots_loop_create.restype = C.c_int
+    lib.uavenv_dqn_slots_loop_create.argtypes = [C.POINTER(UavDqnSlotsLoopConfig), C.POINTER(vp)]
+    lib.uavenv_dqn_slots_loop_destroy.restype = C.c_int
+    lib.uavenv_dqn_slots_loop_destroy.argtypes = [vp]
+    lib.uavenv_dqn_slots_loop_set_eps.restype = C.c_int
+    lib.uavenv_dqn_slots_loop_set_eps.argtypes = [vp, f32]
+    lib.uavenv_dqn_slots_loop_run.restype = C.c_int
+    lib.uavenv_dqn_slots_loop_run.argtypes = [vp, i32, vp]
+    lib.uavenv_dqn_slots_loop_get.restype = C.c_int
+    lib.uavenv_dqn_slots_loop_get.argtypes = [vp, C.POINTER(UavDqnSlotsLoopCursor)]
     if lib.uavenv_abi_version() != ABI_VERSION:
         raise UavEnvError(f"libuavenv ABI {lib.uavenv_abi_version()} != binding {ABI_VERSION}")
     _LIB = lib

@@ -26,6 +26,7 @@
 #include "uavenv_device.hpp"
 #include "qnet_device.hpp"
 #include "dqn_internal.hpp"
+#include "dqn_slots_internal.hpp"
 
 using namespace uav;
 using namespace uavq;
@@ -2100,6 +2101,84 @@ __global__ void __launch_bounds__(256) k_dqn_act_packed(ActArgs g)
     }
 }
 
+// One net per UAV slot on the packed rows of one frame (agent = env * U + slot): k_dqn_act_packed's body, where slice blockIdx.y of
+// the grid stages net y and a lane's env e reads packed row e * U + y.  Same device functions in the same order, so the Q row and
+// the action of agent e * U + y are bit for bit those of k_dqn_act_packed with net y on slot y's rows gathered contiguously, under
+// the key seed + y (the draw is keyed by the env, as there).
+constexpr int kActMaxSlots = 8;
+struct ActSlotsArgs {
+    const void *obs;       // [n_envs * n_nets][20 dwords]
+    int n_envs, n_nets, n_actions, dueling;
+    float eps;
+    uint64_t seed, counter;
+    int32_t *index_out;    // [n_envs * n_nets], by agent
+    float *q_out;          // nullable [n_envs * n_nets][A]
+    struct { const float *local, *img; } net[kActMaxSlots];      // img nullable: q_local's layer 1 of that net in the split form
+};
+
+template <int NMAX>
+__global__ void __launch_bounds__(256) k_dqn_act_slots(ActSlotsArgs g)
+{
+    extern __shared__ __align__(16) float lds[];
+    const W1Split W1 = w1split_at(lds);     // fc1 + b1 in the split form (kTileF floats)
+    float *W2 = lds + kSplitF;              // [16][64]
+    float *b2 = W2 + kMaxOut * kHid;        // [16]
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 15;
+    const int j = (int)blockIdx.y;
+    const float *local = g.net[j].local, *img = g.net[j].img;
+    const uint64_t seed = g.seed + (uint64_t)j;
+    const int n2 = g.n_actions + (g.dueling ? 1 : 0);
+    const NetDev nl = net_view(local, n2);
+    const int e = (int)blockIdx.x * kTile + wv * 16 + r;
+    floatx4 vW[kStageIters];
+    SplitScRegs vS;
+    if (img) img_issue(vW, img); else { w_issue(vW, local); w_issue_sc(vS, local, nl.b1); }
+    float pw[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pw[k] = nl.W2[tid + 256 * k < n2 * kHid ? tid + 256 * k : 0];
+    const float pb2 = nl.b2[tid < n2 ? tid : 0];
+    PRow R;
+    prow_load(R, reinterpret_cast<const uint32_t *>(g.obs) +
+                     ((size_t)(e < g.n_envs ? e : g.n_envs - 1) * (size_t)g.n_nets + (size_t)j) * kPackedDwords);
+    // the epsilon-greedy draw of this lane's env: a serial chain, computed under the loads' round trip
+    const uint4 rn = philox4x32_10(make_uint4((uint32_t)e, (uint32_t)g.counter, (uint32_t)(g.counter >> 32), 0xac7u),
+                                   make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+    if (img) img_commit(lds, vW); else w_commit_split(W1, vW, vS);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (tid + 256 * k < n2 * kHid) W2[tid + 256 * k] = pw[k];
+    if (tid < n2) b2[tid] = pb2;
+    __syncthreads();
+    floatx4 h[4];
+    fwd_strip_split<false>(W1, R, h);
+    float q[NMAX];
+    {
+        W2Frag<NMAX> F;
+        w2_load<NMAX>(F, W2, b2, n2);
+        q_strip<NMAX>(h, F, n2, g.n_actions, g.dueling, q);
+    }
+    if (lane < 16 && e < g.n_envs) {
+        const size_t i = (size_t)e * (size_t)g.n_nets + (size_t)j;
+        if (g.q_out) {
+#pragma unroll
+            for (int a = 0; a < NMAX; ++a)
+                if (a < g.n_actions) g.q_out[i * g.n_actions + a] = q[a];
+        }
+        const float sample = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
+        int a;
+        if (sample > g.eps) {
+            a = 0;
+            float bq = q[0];
+#pragma unroll
+            for (int k = 1; k < NMAX; ++k)
+                if (k < g.n_actions && q[k] > bq) { bq = q[k]; a = k; }
+        } else {
+            a = (int)(((uint64_t)rn.y * (uint64_t)g.n_actions) >> 32);
+        }
+        g.index_out[i] = a;
+    }
+}
+
 // f16 MFMA forward (UavDqnNet.mfma_dtype = 1) on f16 or packed observations.  Workgroups are persistent over tiles (the
 // grid is capped at 512): fc1 is staged and converted once per workgroup, not once per 64 agents, and the next tile's rows
 // are requested before the current tile is computed.
@@ -2244,6 +2323,13 @@ template <int NMAX>
 static int launch_act_packed(const ActArgs &g, int grid, hipStream_t s)
 {
     hipLaunchKernelGGL((k_dqn_act_packed<NMAX>), dim3(grid), dim3(256), kActPLds, s, g);      // 32 KB: no attribute needed
+    return UAVENV_OK;
+}
+
+template <int NMAX>
+static int launch_act_slots(const ActSlotsArgs &g, int grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_dqn_act_slots<NMAX>), dim3(grid, g.n_nets), dim3(256), kActPLds, s, g);   // 32 KB: no attribute needed
     return UAVENV_OK;
 }
 
@@ -2525,6 +2611,45 @@ int uavenv_dqn_act(const UavDqnNet *net, const void *obs_dev, int32_t obs_dtype,
     else rc = small ? launch_act<__half, 4>(g, grid, s) : launch_act<__half, kMaxOut - 2>(g, grid, s);
     if (rc != UAVENV_OK) return rc;
     return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+}
+
+// (internal, csrc/dqn_slots_internal.hpp) images: n_nets pointers (host array, nullable as a whole and per net) to uavenv_dqn_split_image's
+// output for net j as it is now; a net without one converts fc1 while staging -- same values
+int uavenv_dqn_act_slots_img(const UavDqnNet *const *nets, int32_t n_nets, const void *obs_dev, int32_t obs_dtype, int32_t n_envs,
+                             float eps, uint64_t seed, uint64_t counter, int32_t *index_out, float *q_out,
+                             const float *const *images, void *stream)
+{
+    static_assert(kActMaxSlots == UAVENV_DQN_MAX_SLOTS, "include/uavenv.h");
+    if (!nets || n_nets < 1 || n_nets > kActMaxSlots || !obs_dev || !index_out || obs_dtype != UAVENV_OBS_PACKED || n_envs <= 0)
+        return UAVENV_EINVAL;
+    if ((int64_t)n_envs * n_nets >= (1ll << 31) || (((uintptr_t)obs_dev) & 15u) != 0) return UAVENV_EINVAL;
+    ActSlotsArgs g;
+    for (int j = 0; j < kActMaxSlots; ++j) { g.net[j].local = nullptr; g.net[j].img = nullptr; }
+    for (int j = 0; j < n_nets; ++j) {
+        const UavDqnNet *n = nets[j];
+        if (!net_ok(n) || n->mfma_dtype != UAVENV_MFMA_F32 || (((uintptr_t)n->local) & 15u) != 0) return UAVENV_EINVAL;
+        if (n->n_actions != nets[0]->n_actions || (n->dueling != 0) != (nets[0]->dueling != 0)) return UAVENV_EINVAL;
+        g.net[j].local = n->local;
+        if (images && images[j]) {
+            if ((((uintptr_t)images[j]) & 15u) != 0) return UAVENV_EINVAL;
+            g.net[j].img = images[j];
+        }
+    }
+    g.obs = obs_dev; g.n_envs = n_envs; g.n_nets = n_nets; g.n_actions = nets[0]->n_actions; g.dueling = nets[0]->dueling ? 1 : 0;
+    g.eps = eps; g.seed = seed; g.counter = counter;
+    g.index_out = index_out; g.q_out = q_out;
+    const int grid = (n_envs + kTile - 1) / kTile;
+    const bool small = g.n_actions + g.dueling <= 4;
+    const int rc = small ? launch_act_slots<4>(g, grid, (hipStream_t)stream) : launch_act_slots<kMaxOut - 2>(g, grid, (hipStream_t)stream);
+    if (rc != UAVENV_OK) return rc;
+    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+}
+
+int uavenv_dqn_act_slots(const UavDqnNet *const *nets, int32_t n_nets, const void *obs_dev, int32_t obs_dtype, int32_t n_envs,
+                         float eps, uint64_t seed, uint64_t counter, int32_t *index_out_dev, float *q_out_dev, void *stream)
+{
+    return uavenv_dqn_act_slots_img(nets, n_nets, obs_dev, obs_dtype, n_envs, eps, seed, counter, index_out_dev, q_out_dev, nullptr,
+                                    stream);
 }
 
 }  // extern "C"

@@ -694,3 +694,155 @@ int uavenv_sac_loop_run(UavSacLoop *l, int32_t n_steps, void *stream)
 }
 
 }  // extern "C"
+
+// =====================================================================================================================
+// The same loop for the DQN family with one learner per UAV slot (Envs/PathPlan_City.py:59-69: one Trainer per UAV index,
+// each run through run_thread_OffPolicy :364-385): per pass
+//     uavenv_dqn_act_slots          Q(s) + epsilon-greedy of every slot's agents from the packed rows of frame t, one launch
+//     uavenv_step                   Move_Agent for every agent, replay write included
+//     uavenv_replay_draw_slots      (frame, agent) pairs for all slots at once
+//     U x (uavenv_dqn_grad, uavenv_dqn_reduce_adam)       learn_off_policy of slot j on ITS rows
+// Driven from Python this is, per pass and slot, a strided gather, uavenv_dqn_act and a scatter, then the step, then per slot a
+// draw, the gradient and Adam.  Every launch goes through the library's own entry points: K passes from here == K passes of
+// the caller issuing them, bit for bit.  A struct of its own beside UavLoop: that one already serves prioritised replay, the
+// sample lag, both exchanges and the bank refresh, none of which exist here.
+// =====================================================================================================================
+#include "dqn_slots_internal.hpp"
+
+struct UavDqnSlotsLoop {
+    UavDqnSlotsLoopConfig c;
+    int32_t head, filled;
+    int32_t epoch[UAVENV_DQN_MAX_SLOTS];
+    uint64_t counter;
+    size_t obs_row_bytes;
+    // fc1 / b1 of every slot's q_local and q_target in the split form (UavLoop.img has the story): n_slots buffers of
+    // 2 x UAVENV_DQN_IMAGE_FLOATS, rebuilt when a run starts, kept current by the loop's own Adam launches
+    float *img = nullptr;
+};
+
+extern "C" {
+
+int uavenv_dqn_slots_loop_create(const UavDqnSlotsLoopConfig *cfg, UavDqnSlotsLoop **out)
+{
+    if (!cfg || !out || !cfg->env || !cfg->ring.obs || !cfg->ring.action || !cfg->ring.reward || !cfg->ring.done) return UAVENV_EINVAL;
+    if (!cfg->ring.action_is_index || cfg->ring.obs_dtype != UAVENV_OBS_PACKED || cfg->ring.frames < 3 ||
+        cfg->ring.n_agents != uavenv_num_agents(cfg->env))
+        return UAVENV_EINVAL;
+    if (cfg->n_slots < 1 || cfg->n_slots > UAVENV_DQN_MAX_SLOTS || cfg->ring.n_agents % cfg->n_slots != 0) return UAVENV_EINVAL;
+    if (cfg->head < 0 || cfg->head >= cfg->ring.frames || cfg->filled < 0 || cfg->filled > cfg->ring.frames - 1) return UAVENV_EINVAL;
+    if (cfg->batch < 0 || cfg->batch % 64 != 0 || (cfg->batch > 0 && !cfg->draws_dev)) return UAVENV_EINVAL;
+    if (cfg->update_loop <= 0 || (cfg->valid_draws && !cfg->ring.valid)) return UAVENV_EINVAL;
+    for (int j = 0; j < cfg->n_slots; ++j) {
+        const UavDqnSlotsLoopSlot &sl = cfg->slot[j];
+        const UavDqnNet &n = sl.net, &n0 = cfg->slot[0].net;
+        if (!n.local || !n.target || n.mfma_dtype != UAVENV_MFMA_F32 || n.w != 100 || n.hid != 64 || sl.epoch < 0) return UAVENV_EINVAL;
+        if (n.n_actions != n0.n_actions || (n.dueling != 0) != (n0.dueling != 0)) return UAVENV_EINVAL;
+        if (cfg->batch > 0 && (!n.m || !n.v || !sl.partials_dev)) return UAVENV_EINVAL;
+        for (int i = 0; i < j; ++i)
+            if (cfg->slot[i].net.local == n.local || (cfg->batch > 0 && cfg->slot[i].partials_dev == sl.partials_dev)) return UAVENV_EINVAL;
+    }
+    UavDqnSlotsLoop *l = new (std::nothrow) UavDqnSlotsLoop();
+    if (!l) return UAVENV_ENOMEM;
+    l->c = *cfg;
+    l->head = cfg->head;
+    l->filled = cfg->filled;
+    l->counter = cfg->counter;
+    for (int j = 0; j < UAVENV_DQN_MAX_SLOTS; ++j) l->epoch[j] = j < cfg->n_slots ? cfg->slot[j].epoch : 0;
+    l->obs_row_bytes = (size_t)cfg->ring.n_agents * UAVENV_OBS_PACKED_DWORDS * 4;
+    if (hipMalloc((void **)&l->img, (size_t)cfg->n_slots * 2 * UAVENV_DQN_IMAGE_FLOATS * sizeof(float)) != hipSuccess) {
+        delete l;
+        return UAVENV_ENOMEM;
+    }
+    if (cfg->moved_dev && uavenv_set_moved_word(cfg->env, cfg->moved_dev) != UAVENV_OK) {
+        (void)hipFree(l->img);
+        delete l;
+        return UAVENV_EINVAL;
+    }
+    *out = l;
+    return UAVENV_OK;
+}
+
+int uavenv_dqn_slots_loop_destroy(UavDqnSlotsLoop *l)
+{
+    if (!l) return UAVENV_OK;
+    if (l->c.moved_dev) (void)uavenv_set_moved_word(l->c.env, nullptr);
+    if (l->img) (void)hipFree(l->img);
+    delete l;
+    return UAVENV_OK;
+}
+
+int uavenv_dqn_slots_loop_set_eps(UavDqnSlotsLoop *l, float eps)
+{
+    if (!l) return UAVENV_EINVAL;
+    l->c.eps = eps;
+    return UAVENV_OK;
+}
+
+int uavenv_dqn_slots_loop_get(const UavDqnSlotsLoop *l, UavDqnSlotsLoopCursor *out)
+{
+    if (!l || !out) return UAVENV_EINVAL;
+    out->head = l->head;
+    out->filled = l->filled;
+    out->counter = l->counter;
+    for (int j = 0; j < UAVENV_DQN_MAX_SLOTS; ++j) out->epoch[j] = j < l->c.n_slots ? l->epoch[j] : 0;
+    return UAVENV_OK;
+}
+
+int uavenv_dqn_slots_loop_run(UavDqnSlotsLoop *l, int32_t n_steps, void *stream)
+{
+    if (!l || n_steps < 0) return UAVENV_EINVAL;
+    const UavDqnSlotsLoopConfig &c = l->c;
+    const UavReplayRing &R = c.ring;
+    const int U = c.n_slots, B = c.batch;
+    const size_t n = (size_t)R.n_agents;
+    const int envs = R.n_agents / U;
+    hipStream_t s = (hipStream_t)stream;
+    const UavDqnNet *nets[UAVENV_DQN_MAX_SLOTS];
+    float *img[UAVENV_DQN_MAX_SLOTS];
+    for (int j = 0; j < U; ++j) {
+        nets[j] = &c.slot[j].net;
+        img[j] = l->img + (size_t)j * 2 * UAVENV_DQN_IMAGE_FLOATS;
+    }
+    if (n_steps > 0) {                        // whatever happened to the parameters since the last run: the images are rebuilt from them
+        for (int j = 0; j < U; ++j) {
+            const int ri = uavenv_dqn_split_image(nets[j], img[j], s);
+            if (ri != UAVENV_OK) return ri;
+        }
+    }
+    for (int k = 0; k < n_steps; ++k) {
+        const int t = l->head, nxt = t + 1 == R.frames ? 0 : t + 1;
+        int32_t *act_t = (int32_t *)R.action + (size_t)t * n;
+        int rc = uavenv_dqn_act_slots_img(nets, U, (unsigned char *)R.obs + (size_t)t * l->obs_row_bytes, UAVENV_OBS_PACKED, envs, c.eps,
+                                          c.seed, l->counter, act_t, nullptr, img, s);
+        if (rc != UAVENV_OK) return rc;
+        rc = uavenv_set_step_meta(c.env, R.meta ? (unsigned char *)R.meta + (size_t)t * n * UAVENV_META_BYTES : nullptr, nullptr);
+        if (rc != UAVENV_OK) return rc;
+        rc = uavenv_step(c.env, act_t, UAVENV_ACT_INDEX_I32, (unsigned char *)R.obs + (size_t)nxt * l->obs_row_bytes, nullptr,
+                         R.reward + (size_t)t * n, R.done + (size_t)t * n, nullptr, c.info_dev ? c.info_dev + (size_t)t * n : nullptr,
+                         R.valid ? R.valid + (size_t)t * n : nullptr, nullptr, nullptr, c.step_flags, s);
+        if (rc != UAVENV_OK) return rc;
+        l->head = nxt;
+        if (l->filled < R.frames - 1) l->filled += 1;
+        if (B > 0 && (int64_t)l->filled * (int64_t)envs >= (int64_t)(c.learn_start > B ? c.learn_start : B)) {
+            rc = uavenv_replay_draw_slots(R.frames, envs, l->head, l->filled, B, U, c.valid_draws ? R.valid : nullptr, UAVENV_DRAW_MAX_TRIES,
+                                          c.seed + 7, l->counter, c.draws_dev, s);
+            if (rc != UAVENV_OK) return rc;
+            const int rows = uavenv_dqn_partial_rows(B);
+            for (int j = 0; j < U; ++j) {
+                const UavDqnSlotsLoopSlot &sl = c.slot[j];
+                rc = uavenv_dqn_grad_img(&R, l->head, l->filled, B, c.seed, l->counter, c.draws_dev + (size_t)j * B * 2, nets[j], c.kind,
+                                         c.gamma, c.huber, nullptr, nullptr, sl.partials_dev, img[j], s);
+                if (rc != UAVENV_OK) return rc;
+                l->epoch[j] += 1;
+                const int hard = l->epoch[j] % c.update_loop == 0 ? 1 : 0;
+                rc = uavenv_dqn_reduce_adam_img(nets[j], sl.partials_dev, rows, c.lr, c.beta1, c.beta2, c.adam_eps, l->epoch[j], hard,
+                                                sl.loss_dev, nullptr, c.moved_dev, (uint32_t)uavenv_tick(c.env), img[j], s);
+                if (rc != UAVENV_OK) return rc;
+            }
+        }
+        l->counter += 1;
+    }
+    return UAVENV_OK;
+}
+
+}  // extern "C"

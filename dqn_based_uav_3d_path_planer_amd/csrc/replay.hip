@@ -116,6 +116,34 @@ __global__ void k_replay_draw_valid(int frames, int n_envs, int head, int batch,
     }
 }
 
+// Both draws for one learner per UAV slot, as (frame, AGENT) pairs: draw s belongs to slot s / batch and is written as
+// (frame, env * uav + slot).  With a valid plane the positions and the test are k_replay_draw_valid's for n_slots = uav,
+// first_slot = 0; without one, position s alone as in k_replay_draw over batch * uav draws.
+__global__ void k_replay_draw_slots(int frames, int n_envs, int head, int batch, int uav, const unsigned char *__restrict__ valid,
+                                    int max_tries, ReplayPerm perm, int32_t *__restrict__ out)
+{
+    const int total = batch * uav;
+    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < total; s += gridDim.x * blockDim.x) {
+        const int slot = s / batch;
+        int f0 = 0, e0 = 0;
+        if (valid) {
+            bool found = false;
+            for (int t = 0; t < max_tries && !found; ++t) {
+                const uint64_t q = (uint64_t)s + (uint64_t)t * (uint64_t)total;
+                if (q >= (uint64_t)perm.D) break;
+                int f, e;
+                replay_slot_to_frame(perm, replay_perm_apply(perm, (uint32_t)q), head, frames, f, e);
+                if (t == 0) { f0 = f; e0 = e; }
+                if (valid[((size_t)f * n_envs + e) * uav + slot]) { f0 = f; e0 = e; found = true; }
+            }
+        } else {
+            replay_slot_to_frame(perm, replay_perm_apply(perm, (uint32_t)s), head, frames, f0, e0);
+        }
+        out[2 * s] = f0;
+        out[2 * s + 1] = e0 * uav + slot;
+    }
+}
+
 // Trainer/DuelingDQN_Trainer.py:86-97: sample > eps -> argmax_a Q(s,a) (first maximum, as torch.max), else randrange(A).
 __global__ void k_select_actions(const float *__restrict__ q, int n, int A, float eps, uint64_t seed, uint64_t counter,
                                  int32_t *__restrict__ idx_out, float *__restrict__ steer_out)
@@ -219,6 +247,23 @@ int uavenv_replay_draw_valid(int32_t frames, int32_t n_envs, int32_t head, int32
     hipLaunchKernelGGL(k_replay_draw_valid, dim3(grid), dim3(block), 0, (hipStream_t)stream, frames, n_envs, head, batch, n_slots,
                        uav_per_env, first_slot, valid, max_tries,
                        replay_perm(seed, counter, (uint32_t)filled * (uint32_t)n_envs, (uint32_t)n_envs), frame_agent_out);
+    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+}
+
+int uavenv_replay_draw_slots(int32_t frames, int32_t n_envs, int32_t head, int32_t filled, int32_t batch, int32_t uav_per_env,
+                             const uint8_t *valid, int32_t max_tries, uint64_t seed, uint64_t counter, int32_t *frame_agent_out,
+                             void *stream)
+{
+    if (!frame_agent_out || frames < 2 || n_envs <= 0 || batch <= 0 || uav_per_env <= 0 || (valid && max_tries <= 0) || filled <= 0 ||
+        filled > frames - 1 || head < 0 || head >= frames || (uint64_t)filled * (uint64_t)n_envs >= (1ull << 32) ||
+        (int64_t)batch * uav_per_env >= (1ll << 31) || (int64_t)n_envs * uav_per_env >= (1ll << 31))
+        return UAVENV_EINVAL;
+    const int block = 256;
+    int grid = (batch * uav_per_env + block - 1) / block;
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(k_replay_draw_slots, dim3(grid), dim3(block), 0, (hipStream_t)stream, frames, n_envs, head, batch, uav_per_env,
+                       valid, max_tries, replay_perm(seed, counter, (uint32_t)filled * (uint32_t)n_envs, (uint32_t)n_envs),
+                       frame_agent_out);
     return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
 }
 

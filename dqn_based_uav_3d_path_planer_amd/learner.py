@@ -548,3 +548,61 @@ class FusedDQNLearner:
                                       self.eps, self.epoch, hard, self.loss.data_ptr(), s)
         _lib.check(rc, "uavenv_dqn_adam")
         return self.loss
+
+
+def check_slot_learners(learners, n_slots: int = None) -> list:
+    """The list-level conditions of the one-net-per-UAV-slot kernels (uavenv_dqn_act_slots, the slots loop), checked on the
+    Python objects alone -- before anything reaches the library: 1 .. 8 distinct learners (n_slots of them when given) of one
+    n_actions / head shape, all on the f32 MFMA.  Returns the list."""
+    from . import _lib
+    ls = list(learners) if learners is not None else []
+    if not ls or len(ls) > _lib.DQN_MAX_SLOTS:
+        raise ValueError("one fused DQN learner per UAV slot: 1 to %d of them" % _lib.DQN_MAX_SLOTS)
+    if n_slots is not None and len(ls) != int(n_slots):
+        raise ValueError(f"{len(ls)} learners for {int(n_slots)} UAV slots: one learner per slot")
+    if len({id(L) for L in ls}) != len(ls):
+        raise ValueError("the slots' learners must be distinct objects (one Trainer per UAV index)")
+    L0 = ls[0]
+    for L in ls:
+        if not all(hasattr(L, a) for a in ("net", "flat", "n_actions", "dueling", "mfma")):
+            raise ValueError("the slots' learners must be FusedDQNLearner objects")
+        if L.mfma != "f32":
+            raise ValueError("the slot kernels take f32-MFMA learners only")
+        if (L.n_actions, bool(L.dueling)) != (L0.n_actions, bool(L0.dueling)):
+            raise ValueError("the slots' learners must share n_actions and the head shape (plain / dueling)")
+    return ls
+
+
+def act_slots(learners, obs: torch.Tensor, eps: float, seed: int, counter: int, index_out: torch.Tensor,
+              q_out: torch.Tensor = None, images=None):
+    """Q(s) + epsilon-greedy of one learner per UAV slot on the packed rows of one frame (agent = env * U + slot) in ONE launch
+    (uavenv_dqn_act_slots): agent e * U + j gets what learners[j].act(obs[j::U].contiguous(), eps, seed + j, counter) gives at
+    index e, bit for bit.  index_out int32 [N], q_out (optional) f32 [N, A], both by agent.  images: one split_image() tensor
+    per learner (or None) -- the form the slots loop launches, same results."""
+    import ctypes as C
+    from . import _lib
+    ls = check_slot_learners(learners)
+    U = len(ls)
+    if obs.dtype != torch.int32 or obs.dim() != 2 or obs.shape[1] != _lib.PACKED_DWORDS or not obs.is_contiguous():
+        raise ValueError("act_slots takes contiguous packed rows (int32 [N, 20])")
+    N = int(obs.shape[0])
+    if N <= 0 or N % U:
+        raise ValueError(f"{N} rows do not divide into {U} UAV slots")
+    if index_out is None or index_out.dtype != torch.int32 or index_out.numel() != N or not index_out.is_contiguous():
+        raise ValueError("index_out must be a contiguous int32 tensor with one element per agent")
+    if q_out is not None and (q_out.dtype != torch.float32 or q_out.numel() != N * ls[0].n_actions or not q_out.is_contiguous()):
+        raise ValueError("q_out must be a contiguous float32 [N, n_actions] tensor")
+    if images is not None and len(images) != U:
+        raise ValueError("images: one per learner")
+    lib = _lib.load()
+    nets = (C.POINTER(_lib.UavDqnNet) * U)(*[C.pointer(L.net) for L in ls])
+    s = torch.cuda.current_stream(obs.device).cuda_stream
+    qp = None if q_out is None else q_out.data_ptr()
+    if images is None:
+        rc = lib.uavenv_dqn_act_slots(nets, U, obs.data_ptr(), _lib.OBS_PACKED, N // U, float(eps), int(seed) & (2 ** 64 - 1),
+                                      int(counter), index_out.data_ptr(), qp, s)
+    else:
+        imgs = (C.c_void_p * U)(*[None if t is None else t.data_ptr() for t in images])
+        rc = lib.uavenv_dqn_act_slots_img(nets, U, obs.data_ptr(), _lib.OBS_PACKED, N // U, float(eps), int(seed) & (2 ** 64 - 1),
+                                          int(counter), index_out.data_ptr(), qp, imgs, s)
+    _lib.check(rc, "uavenv_dqn_act_slots")

@@ -343,3 +343,109 @@ class SACHotLoop:
                 p.beta = float(beta[j])
                 p.n_entries = self.ring.filled * n_envs
                 p._dirty = True
+
+
+class DQNSlotsHotLoop:
+    """The off-policy loop with one fused DQN-family learner per UAV slot (Envs/PathPlan_City.py:59-69, :364-385), enqueued by
+    csrc/loop.hip: per pass ONE act launch for all slots (uavenv_dqn_act_slots), the env step (replay write included), ONE draw
+    of (frame, agent) pairs for all slots and per slot the gradient and Adam launches -- what the general run_eposide issues
+    from Python slot by slot, without the interpreter between the launches.  Uniform replay on one GPU.  The ring cursor and the
+    learners' update counts live in the C object while the loop exists; `run` writes them back.  The learners' parameters may
+    be replaced between two runs (a federated merge): every run rebuilds the layer-1 images its launches stage."""
+
+    def __init__(self, ring: DeviceReplayRing, learners, batch: int, seed: int, eps: float = 0.1, counter: int = 0,
+                 learn_start: int = 0, auto_reset: bool = True, skip_done: bool = True, info: torch.Tensor = None,
+                 gate_updates: bool = False, valid_draws: bool = None):
+        """valid_draws (default: on when finished agents are skipped and not restarted): the draws go over the valid rows only
+        (the reference never stores a row for a finished agent, Envs/PathPlan_City.py:456-459); gate_updates: no update of any
+        slot behind a step that moved nobody (HotLoop has the story)."""
+        from .learner import check_slot_learners
+        # every check on the Python objects first: nothing below this block fails for a reason the caller could have known
+        if not ring.discrete or not ring.env.packed:
+            raise ValueError("DQNSlotsHotLoop drives the discrete (DQN-family) path on a packed ring")
+        env = ring.env
+        ls = check_slot_learners(learners, env.uav_per_env)
+        if batch < 0 or batch % 64:
+            raise ValueError("batch must be a multiple of 64")
+        L0 = ls[0]
+        hyper = lambda L: (L.kind, L.huber, L.update_loop, L.gamma, L.lr, tuple(L.betas), L.eps)
+        for L in ls:         # one Trainer.xml: the slots share kind and hyper-parameters
+            if hyper(L) != hyper(L0):
+                raise ValueError("the slots' learners must share their kind and hyper-parameters")
+        if valid_draws is None:
+            valid_draws = bool(skip_done) and not auto_reset
+        if valid_draws and not skip_done:
+            raise ValueError("valid_draws needs skip_done (with auto-reset every stored row is valid)")
+        if info is not None and not (info.dtype == torch.uint8 and tuple(info.shape) == (ring.frames, env.N) and info.is_contiguous()):
+            raise ValueError("info must be a contiguous uint8 [frames, N] plane")
+        self.lib = _lib.load()
+        self.ring, self.learners = ring, ls
+        U, d = len(ls), env.device
+        self._draws = torch.zeros((U * max(int(batch), 1), 2), dtype=torch.int32, device=d)
+        self._partials = [L.new_partials(max(int(batch), 64)) for L in ls]      # every slot's own rows
+        cfg = _lib.UavDqnSlotsLoopConfig()
+        cfg.env = env._h
+        cfg.ring = ring._c
+        if info is not None:
+            cfg.info_dev = info.data_ptr()
+        self._moved = torch.zeros(1, dtype=torch.int32, device=d) if gate_updates else None
+        if self._moved is not None:
+            cfg.moved_dev = self._moved.data_ptr()
+        cfg.draws_dev = self._draws.data_ptr()
+        cfg.n_slots, cfg.batch = U, int(batch)
+        cfg.head, cfg.filled = ring.head, ring.filled
+        cfg.kind = 0 if L0.kind == "dqn" else 1
+        cfg.huber, cfg.update_loop, cfg.learn_start = L0.huber, L0.update_loop, int(learn_start)
+        cfg.valid_draws = int(bool(valid_draws))
+        cfg.step_flags = (_lib.STEP_AUTO_RESET if auto_reset else 0) | (_lib.STEP_SKIP_DONE if skip_done else 0) | ring.extra_flags
+        cfg.seed, cfg.counter = int(seed), int(counter)
+        cfg.eps, cfg.gamma, cfg.lr = float(eps), L0.gamma, L0.lr
+        cfg.beta1, cfg.beta2, cfg.adam_eps = L0.betas[0], L0.betas[1], L0.eps
+        for j, L in enumerate(ls):
+            sl = cfg.slot[j]
+            sl.net = L.net
+            sl.partials_dev = self._partials[j].data_ptr()
+            sl.loss_dev = L.loss.data_ptr()
+            sl.epoch = L.epoch
+        self._keep = info
+        self._h = C.c_void_p()
+        _lib.check(self.lib.uavenv_dqn_slots_loop_create(C.byref(cfg), C.byref(self._h)), "uavenv_dqn_slots_loop_create")
+        self.counter = int(counter)
+        self.batch = int(batch)
+        self._seen = (ring.head, ring.filled, tuple(L.epoch for L in ls))
+
+    def in_sync(self, batch: int = None) -> bool:
+        """As HotLoop.in_sync: False when the ring cursor or a learner's update count moved on the Python side since the last
+        run(), or another batch size is asked for -- the owner then closes this loop and creates a new one."""
+        return (self._seen == (self.ring.head, self.ring.filled, tuple(L.epoch for L in self.learners)) and
+                (batch is None or int(batch) == self.batch))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.uavenv_dqn_slots_loop_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_eps(self, eps: float):
+        _lib.check(self.lib.uavenv_dqn_slots_loop_set_eps(self._h, float(eps)), "uavenv_dqn_slots_loop_set_eps")
+
+    def run(self, n_steps: int):
+        """Enqueue n_steps passes on the current torch stream (asynchronous)."""
+        s = torch.cuda.current_stream(self.ring.env.device).cuda_stream
+        rc = self.lib.uavenv_dqn_slots_loop_run(self._h, int(n_steps), s)
+        self._sync_cursor()              # (the passes before a failure are in the ring and in the learners' counters)
+        _lib.check(rc, "uavenv_dqn_slots_loop_run")
+
+    def _sync_cursor(self):
+        cur = _lib.UavDqnSlotsLoopCursor()
+        _lib.check(self.lib.uavenv_dqn_slots_loop_get(self._h, C.byref(cur)), "uavenv_dqn_slots_loop_get")
+        self.ring.head, self.ring.filled = cur.head, cur.filled
+        self.counter = int(cur.counter)
+        for j, L in enumerate(self.learners):
+            L.epoch = int(cur.epoch[j])
+        self._seen = (cur.head, cur.filled, tuple(L.epoch for L in self.learners))

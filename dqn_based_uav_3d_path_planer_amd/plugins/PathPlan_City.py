@@ -99,9 +99,25 @@ class PathPlan_City:
                                int(None2Value(sacp.get("IS_Continuous"), 0)) == 1 and param.get("obs_dtype") is None and
                                int(None2Value(tcfg.get("Batch_Size"), 128)) % 64 == 0 and
                                int(None2Value(tcfg.get("fused"), 1)) != 0 and torch.cuda.is_available())
+        # <fused_slots>1</fused_slots> with num_UAV > 1: one fused DQN-family learner per UAV slot, the whole pass enqueued from C
+        # (csrc/loop.hip: UavDqnSlotsLoop).  Off by default: the general path below draws epsilon-greedy from torch's generator and
+        # existing configurations reproduce under torch.manual_seed; this path draws from Philox.  Everything the loop needs is
+        # checked HERE (the trainers then come up fused on the f32 MFMA); when a condition fails the general path runs.
+        n2 = n_actions + (1 if tcfg.get("Trainer_Type") == "DuelingDQN_Trainer" else 0)
+        self._want_fast_slots = (int(None2Value(param.get("fast_path"), 1)) != 0 and int(None2Value(param.get("fused_slots"), 0)) != 0 and
+                                 1 < self.num_UAV <= 8 and
+                                 (tcfg.get("Trainer_Type") in ("DQN_Trainer", "DDQN_Trainer", "DuelingDQN_Trainer")) and
+                                 param.get("obs_dtype") is None and
+                                 int(None2Value(tcfg.get("Batch_Size"), 128)) % 64 == 0 and
+                                 int(None2Value(tcfg.get("fused"), 1)) != 0 and (tcfg.get("mfma") or "f32") == "f32" and
+                                 int(None2Value(tcfg.get("IsPriority_Replay"), 0)) == 0 and
+                                 int(None2Value(tcfg.get("w"), 1)) == 100 and int(None2Value(tcfg.get("hiden_dim"), 64)) == 64 and
+                                 n_actions >= 2 and n2 + 2 <= 16 and
+                                 str(tcfg.get("device") or param.get("device") or "cuda").startswith("cuda") and
+                                 torch.cuda.is_available())
         if self.Is_On_Policy == 1:
-            self._want_fast = self._want_fast_sac = False
-        if self._want_fast or self._want_fast_sac:
+            self._want_fast = self._want_fast_sac = self._want_fast_slots = False
+        if self._want_fast or self._want_fast_sac or self._want_fast_slots:
             obs_dtype = "packed"
         fp = (uav_params.get("Power_param") or {}).get("Fly_power") or {}
         power = tuple(float(fp.get(k)) for k in ("P_i", "v_0", "d_0", "rho", "s", "A", "P_b", "F_b")) \
@@ -212,9 +228,21 @@ class PathPlan_City:
             self._sac_counter = 0
             for u in self.Agents:
                 u.Trainer.replay_memory = _RingMemoryView(ring, per_frame=self.num_envs)
+        self.fast_slots = bool(self._want_fast_slots and getattr(self.backend, "packed", False) and
+                               all(getattr(u.Trainer, "fused", False) and getattr(u.Trainer.learner, "mfma", None) == "f32" and
+                                   getattr(u.Trainer, "IsPriority_Replay", 0) == 0 for u in self.Agents))
+        self._slots_hot, self._slots_counter = None, 0
+        if self.fast_slots:
+            # one packed ring for all UAV slots, as the SAC path keeps it: slot j's replay memory is rows e * num_UAV + j of every
+            # frame -- num_envs transitions per frame, replay_size transitions per trainer (one ReplayMemory per UAV)
+            from dqn_based_uav_3d_path_planer_amd.replay import DeviceReplayRing
+            self._ring = DeviceReplayRing(self.backend, max(tr0.replay_size * self.num_UAV, 2 * self.backend.N), discrete=True)
+            self._info = torch.zeros((self._ring.frames, self.backend.N), dtype=torch.uint8, device=self.backend.device)
+            for u in self.Agents:
+                u.Trainer.replay_memory = _RingMemoryView(self._ring, per_frame=self.num_envs)
         # UAV.path of env 0 (UAV.py:431) and the path.csv the reference rewrites at every terminal (:461-464,:479-483,
         # :505-509).  One 16-double read-back of env 0's agents per step; <record_path>0</record_path> turns it off.
-        self.record_path = int(None2Value(param.get("record_path"), 0 if (self.fast or self.fast_sac) else 1))
+        self.record_path = int(None2Value(param.get("record_path"), 0 if (self.fast or self.fast_sac or self.fast_slots) else 1))
         self.path_csv = None2Value(param.get("path_csv"), "path.csv")
         self._paths = [[] for _ in range(self.num_UAV)]
         self._path_done = [False] * self.num_UAV
@@ -584,6 +612,88 @@ class PathPlan_City:
         self._federated_merge()
         return self.result
 
+    def _run_eposide_fused_slots(self, eps_rate):
+        """run_eposide with one fused DQN-family trainer per UAV slot (<fused_slots>1</fused_slots>, num_UAV > 1):
+        DQNSlotsHotLoop enqueues done_check passes at a time -- one act launch for all slots on the packed rows of the current
+        frame, the env step (replay write included), one draw of every slot's Batch_Size transitions over ITS valid rows, and
+        per slot the gradient and Adam launches (:364-385, :456).  The host reads back, every done_check passes, how many agents
+        each step moved and the info counts, as _run_eposide_fused; updates behind a step that moved nobody are gated off on the
+        device, and the counters follow."""
+        from dqn_based_uav_3d_path_planer_amd.loop import DQNSlotsHotLoop
+        self.Reset_Result(eps_rate)
+        ring, U = self._ring, self.num_UAV
+        trs = [u.Trainer for u in self.Agents]
+        Ls = [t_.learner for t_ in trs]
+        self._episode += 1
+        self._refresh_bank()
+        self.backend.reset(self.seed + self._episode, obs=ring.obs[ring.head])      # UAV.reset everywhere; the replay stays
+        self._obs_raw = ring.obs[ring.head]
+        self._invalidate()
+        self._paths, self._path_done = [[] for _ in range(U)], [False] * U
+        train = all(t_.Is_Train for t_ in trs)
+        batch_now = trs[0].Batch_Size if train else 0
+        if self._slots_hot is not None and not self._slots_hot.in_sync(batch_now):
+            self._slots_counter = self._slots_hot.counter    # the Philox stream goes on where the old loop stopped
+            self._slots_hot.close()      # Is_Train / Batch_Size / the cursor / an epoch changed behind the C object
+            self._slots_hot = None
+        if self._slots_hot is None:
+            self._slots_hot = DQNSlotsHotLoop(ring, Ls, batch_now, seed=self.seed, eps=eps_rate, counter=self._slots_counter,
+                                              learn_start=trs[0].Batch_Size + 1, auto_reset=False, skip_done=True, info=self._info,
+                                              gate_updates=True)
+        hot = self._slots_hot
+        hot.set_eps(eps_rate if train else 0.0)
+        k = 1 if self.record_path else min(self.done_check, ring.frames - 2)
+        n_steps, ended, passes = 0, False, 0
+        dev = self.backend.device
+        epoch0 = [L.epoch for L in Ls]
+        while not ended:
+            t0 = ring.head
+            hot.run(k)
+            passes += k
+            fr = (t0 + torch.arange(k, device=dev)) % ring.frames
+            v = ring.valid[fr].bool()                                                # [k, N] agents moved by each step
+            inf = self._info[fr]
+            stats = torch.stack([v.sum(1)] + [((inf == c) & v).sum(1) for c in range(3)], 1).cpu().numpy()   # one sync
+            for i in range(k):
+                if stats[i, 0] == 0:                                                 # nobody moved: finished before this step
+                    ended = True
+                    break
+                n_steps += 1
+                self.result["normal"] += int(stats[i, 1])
+                self.result["success"] += int(stats[i, 2])
+                self.result["lose"] += int(stats[i, 3])
+            self._obs_raw = ring.obs[ring.head]
+            self._invalidate()
+            if self.record_path:
+                self._record_paths(range(U))
+        surplus = passes - n_steps
+        for L, e0 in zip(Ls, epoch0):        # the gated passes changed nothing on the device: one update per moving step
+            L.epoch -= min(surplus, L.epoch - e0)
+        self.surplus_passes_last_episode = surplus
+        self._slots_counter = hot.counter - surplus
+        if surplus > 0:                      # ... and neither the replay cursor nor the Philox counter remembers them
+            hot.close()
+            self._slots_hot = None
+            self._rewind_ring(surplus)
+        items = []
+        for uav in self.Agents:
+            tr = uav.Trainer
+            tr.loss = tr.learner.loss
+            items.append({"loss": tr.learner.loss, "sum_epoch": tr.epoch, "score": uav.score, "average_score": uav.score,
+                          "step": uav.Step, "energy_cost": uav.energy_cost_total, "task_collect": uav.task_collect,
+                          "Energy_Efficent": uav.task_collect / (uav.energy_cost_total + 0.001), "UE_waiting_time": 0})
+            if tr.Is_Train and tr.epoch // tr.save_loop != getattr(tr, "_saved_at", 0):
+                tr._saved_at = tr.epoch // tr.save_loop
+                tr.save()
+        self.Train_statistics(items)
+        self.steps_last_episode = n_steps
+        self.epoch += 1
+        if self.epoch % self.print_loop == 0:
+            for uav in self.Agents:
+                uav.record_list()
+        self._federated_merge()
+        return self.result
+
     def _run_eposide_fused_sac(self, eps_rate):
         """run_eposide with one fused SAC trainer per UAV slot (BASELINE configs[3]'s shape): per time step, one
         uavenv_sac_act launch per slot on the packed rows of the current frame -> the env step (replay write included) ->
@@ -835,6 +945,8 @@ class PathPlan_City:
             return self._run_eposide_fused(eps_rate)
         if self.fast_sac:
             return self._run_eposide_fused_sac(eps_rate)
+        if self.fast_slots:
+            return self._run_eposide_fused_slots(eps_rate)
         self.Reset_Result(eps_rate)
         self.Scene_Random_Reset()
         names = ("normal", "success", "lose")

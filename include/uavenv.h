@@ -269,6 +269,14 @@ int uavenv_replay_draw(int32_t frames, int32_t n_agents, int32_t head, int32_t f
 int uavenv_replay_draw_valid(int32_t frames, int32_t n_envs, int32_t head, int32_t filled, int32_t batch, int32_t n_slots,
                              int32_t uav_per_env, int32_t first_slot, const uint8_t *valid_dev, int32_t max_tries, uint64_t seed,
                              uint64_t counter, int32_t *frame_env_out_dev, void *stream);
+/* The draws of all uav_per_env slots as (frame, AGENT) pairs, one launch: slot j's draws [j * batch, (j + 1) * batch) are written as
+ * (frame, env * uav_per_env + j) -- uavenv_dqn_grad takes slice j as its explicit pairs.  Frame and env are those of
+ * uavenv_replay_draw_valid(frames, n_envs, head, filled, batch, uav_per_env, uav_per_env, 0, valid_dev, max_tries, seed, counter)
+ * with a valid plane, and of uavenv_replay_draw(frames, n_envs, head, filled, uav_per_env * batch, seed, counter) with
+ * valid_dev NULL (max_tries is not looked at then). */
+int uavenv_replay_draw_slots(int32_t frames, int32_t n_envs, int32_t head, int32_t filled, int32_t batch, int32_t uav_per_env,
+                             const uint8_t *valid_dev, int32_t max_tries, uint64_t seed, uint64_t counter,
+                             int32_t *frame_agent_out_dev, void *stream);
 
 /* epsilon-greedy over Q-values (Trainer/DuelingDQN_Trainer.py:86-97): q_dev N x A f32 (row-major).
  * Writes the chosen index (int32, nullable) and its steering value (f32, nullable). */
@@ -396,6 +404,16 @@ int uavenv_dqn_reduce_adam(const UavDqnNet *net, const float *partials_dev, int3
 /* Q(s) for n envs + epsilon-greedy in one launch (DuelingDQN_Trainer.py:86-97); q_out_dev nullable [n][A]. */
 int uavenv_dqn_act(const UavDqnNet *net, const void *obs_dev, int32_t obs_dtype, int32_t n, float eps, uint64_t seed,
                    uint64_t counter, int32_t *index_out_dev, float *steer_out_dev, float *q_out_dev, void *stream);
+/* The same for one net per UAV slot in ONE launch: obs_dev holds n_envs * n_nets packed rows (UAVENV_OBS_PACKED only), agent
+ * e * n_nets + j is flown by nets[j] (host array).  index_out_dev [n_envs * n_nets] and q_out_dev (nullable, [n_envs * n_nets][A])
+ * are indexed by agent.  For agent e * n_nets + j the action and the Q row are bit for bit what
+ * uavenv_dqn_act(nets[j], rows j, j + n_nets, ... gathered contiguously, UAVENV_OBS_PACKED, n_envs, eps, seed + j, counter, ...)
+ * gives at index e: the draw is Philox(seed + j (mod 2^64); e, counter, 0xac7).  UAVENV_EINVAL, with nothing enqueued, for
+ * n_nets < 1 or > UAVENV_DQN_MAX_SLOTS, a NULL net, another obs_dtype, an f16-MFMA net, nets that differ in n_actions or dueling,
+ * a head uavenv_dqn_act refuses, a `local` or obs_dev off 16 bytes, n_envs <= 0. */
+#define UAVENV_DQN_MAX_SLOTS 8
+int uavenv_dqn_act_slots(const UavDqnNet *const *nets, int32_t n_nets, const void *obs_dev, int32_t obs_dtype, int32_t n_envs,
+                         float eps, uint64_t seed, uint64_t counter, int32_t *index_out_dev, float *q_out_dev, void *stream);
 
 /* ---- greedy policy evaluation: whole episodes in one launch (Trainer/DuelingDQN_Trainer.py:90, Is_Train == 0) ----------------
  * Episode e (0 <= e < n) flies scenario row (first + e) mod m of a scenario set -- the env's bank (start_goal / sub / nsub NULL) or
@@ -843,6 +861,55 @@ int uavenv_sac_loop_run(UavSacLoop *loop, int32_t n_steps, void *stream);
 int uavenv_sac_loop_get(const UavSacLoop *loop, UavSacLoopCursor *out);
 /* ReplayTree.beta of every slot as the loop left it (n_slots doubles). */
 int uavenv_sac_loop_get_per(const UavSacLoop *loop, double *beta_out);
+
+/* ---- the off-policy loop for the DQN family with one learner per UAV slot, enqueued from C ------------------------------
+ * PathPlan_City.run_thread_OffPolicy (Envs/PathPlan_City.py:364-385) with one Trainer per UAV index (:59-69) for every env at
+ * once, K passes per call.  Pass t with counter c, on a packed discrete ring whose n_agents = n_envs * n_slots:
+ *     uavenv_dqn_act_slots     all slots' Q(s) + epsilon-greedy from frame t's rows into frame t's action plane (key `seed`)
+ *     uavenv_step              UAVENV_ACT_INDEX_I32, replay write into frame t + 1 (transition records included)
+ *     while batch > 0 and filled * n_envs >= max(learn_start, batch):
+ *     uavenv_replay_draw_slots (seed + 7, c) into draws_dev: over the valid rows with valid_draws, over every stored row otherwise
+ *     per slot j               uavenv_dqn_grad on slice j of the draws with net j, epoch j += 1, hard copy every update_loop
+ *                              updates, uavenv_dqn_reduce_adam_gated (gated on moved_dev when given)
+ * -- 3 + 2 n_slots launches, bit for bit what the same entry points give when the caller issues them.  The loop owns one layer-1
+ * image per slot (the split form its act and gradient launches stage): rebuilt from the parameters whenever a run with
+ * n_steps > 0 starts, kept current by its own Adam launches, so parameters may be replaced BETWEEN runs (a federated merge).
+ * Uniform replay on one GPU only: no prioritised replay, no gradient exchange, no sample lag, no bank refresh. */
+typedef struct UavDqnSlotsLoopSlot {
+    UavDqnNet net;               /* f32 MFMA, w 100, hid 64; all slots one n_actions / dueling */
+    float *partials_dev;         /* uavenv_dqn_partial_rows(batch) x uavenv_dqn_partial_stride(net) floats, this slot's own */
+    float *loss_dev;             /* device scalar: mean loss of this slot's last update */
+    int32_t epoch;               /* updates done so far (Adam's step count) */
+    int32_t reserved0;
+} UavDqnSlotsLoopSlot;
+typedef struct UavDqnSlotsLoopConfig {
+    UavEnv *env;
+    UavReplayRing ring;          /* UAVENV_OBS_PACKED, action_is_index = 1, n_agents = n_envs * n_slots */
+    uint8_t *info_dev;           /* nullable: frames x N plane of uavenv_step's info codes */
+    uint32_t *moved_dev;         /* nullable, as UavLoopConfig.moved_dev: no update of any slot behind a step that moved nobody */
+    int32_t *draws_dev;          /* n_slots x batch x 2 (frame, agent); may be NULL when batch == 0 */
+    int32_t n_slots;             /* = uav_per_env: slot j acts for and learns from agents e * n_slots + j */
+    int32_t batch;               /* per slot, multiple of 64; 0 = rollout only */
+    int32_t head, filled;
+    int32_t kind, huber, update_loop, learn_start;
+    int32_t valid_draws;         /* != 0 (needs ring.valid): draws over the VALID rows only, for loops that skip finished agents */
+    uint32_t step_flags;
+    uint64_t seed, counter;
+    float eps, gamma, lr, beta1, beta2, adam_eps;
+    UavDqnSlotsLoopSlot slot[UAVENV_DQN_MAX_SLOTS];
+} UavDqnSlotsLoopConfig;
+typedef struct UavDqnSlotsLoopCursor {
+    int32_t head, filled;
+    uint64_t counter;
+    int32_t epoch[UAVENV_DQN_MAX_SLOTS];
+} UavDqnSlotsLoopCursor;
+typedef struct UavDqnSlotsLoop UavDqnSlotsLoop;
+int uavenv_dqn_slots_loop_create(const UavDqnSlotsLoopConfig *cfg, UavDqnSlotsLoop **out);
+int uavenv_dqn_slots_loop_destroy(UavDqnSlotsLoop *loop);
+int uavenv_dqn_slots_loop_set_eps(UavDqnSlotsLoop *loop, float eps);
+/* Enqueue n_steps passes on `stream`; never synchronises. */
+int uavenv_dqn_slots_loop_run(UavDqnSlotsLoop *loop, int32_t n_steps, void *stream);
+int uavenv_dqn_slots_loop_get(const UavDqnSlotsLoop *loop, UavDqnSlotsLoopCursor *out);
 
 /* ---- federated merge of the per-UAV trainers (Envs/PathPlan_City.py:469-475 -> Federated_Learning_AC :590-601) --------------
  * Every one of the n_blocks flat f32 parameter blocks (device pointers, 16-byte aligned, distinct, n_floats each; the array
