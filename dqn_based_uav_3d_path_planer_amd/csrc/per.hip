@@ -129,7 +129,8 @@ __global__ void __launch_bounds__(256) k_per_sample(UavPer p, int n_chunks, int 
     }
     // chunk: the first b with v <= prefix[b + 1] and something in front of that boundary (wave-uniform binary search).
     // A draw past the total (caller's stream, or rounding of seg * batch) is pulled back onto it, and a draw of exactly 0
-    // skips leading all-zero chunks: either would otherwise end in a chunk without a single positive priority.
+    // skips leading all-zero chunks: either would otherwise end in a chunk without a single positive priority.  So a draw of
+    // 0 takes the FIRST leaf with a positive priority (the reference's descent would end on leaf 0 whatever it holds).
     const double total = p.chunk_prefix[n_chunks];
     v = v < total ? v : total;
     // The predicate "v <= prefix[b + 1] and prefix[b + 1] > 0" is monotone in b; the first b that satisfies it is found by the
@@ -177,7 +178,9 @@ __global__ void __launch_bounds__(256) k_per_sample(UavPer p, int n_chunks, int 
         if (lane >= off) incl += up;
     }
     const double excl = incl - s;
-    const unsigned long long hit = __ballot(r <= incl);
+    // (incl > 0: a draw of exactly 0 -- r == 0 -- is owned by the first lane with something in it, like the chunk search above;
+    //  lane 0 with sixteen empty leaves would send it to the fall-back's LAST positive leaf.  r > 0 already implies incl > 0.)
+    const unsigned long long hit = __ballot(r <= incl && incl > 0.0);
     int owner = hit ? __builtin_ctzll(hit) : 63;
     int64_t q = -1;
     double pq = 0.0;

@@ -84,12 +84,16 @@ def leaf_rotation(capacity):
     return (1 << depth) - capacity
 
 
-def sample_by_cumsum(prio, total_for_nothing, draws):
+def sample_by_cumsum(prio, total_for_nothing, draws, rot=None):
     """The same selection without a tree: first in-order position whose inclusive cumulative priority reaches v
-    (what csrc/per.hip does).  Agrees with the descent except when v falls within rounding of a boundary."""
+    (what csrc/per.hip does).  Agrees with the descent except when v falls within rounding of a boundary, and for a draw of
+    exactly 0 in front of empty leaves: the descent ends on leaf 0 whatever it holds, the device on the first leaf with a
+    positive priority (it never returns an empty leaf while one is filled).  rot: the in-order rotation (default: the flat
+    tree's, leaf_rotation; 0 = DevicePER(tree_order=False))."""
     c = len(prio)
-    rot = leaf_rotation(c)
+    rot = leaf_rotation(c) if rot is None else int(rot)
     order = (np.arange(c) + rot) % c
     cs = np.cumsum(prio[order])
-    q = np.searchsorted(cs, np.asarray(draws), side="left")
+    v = np.asarray(draws)
+    q = np.where(v > 0, np.searchsorted(cs, v, side="left"), np.searchsorted(cs, 0.0, side="right"))
     return order[np.minimum(q, c - 1)]

@@ -9,6 +9,12 @@
   of the D = filled * n_agents stored transitions (6-round alternating Feistel network over ceil(log2 D) bits,
   cycle-walked into [0, D); csrc/uavenv_device.hpp: replay_perm / replay_perm_apply).
 * act_draws: the epsilon-greedy stream of uavenv_dqn_act / uavenv_select_actions (DuelingDQN_Trainer.py:86-97).
+* the other seven device streams ("Random streams"), written from include/uavenv.h, DESIGN.md and the kernels' comments:
+  randn (uavenv_randn: every rsample() of SAC training), eval_noise (evaluate.sac_noise / the SAC evaluation's sample mode),
+  per_draws (the stratified draws of uavenv_per_sample), reset_draws (uavenv_reset_all and the step's auto-reset),
+  eval_headings / eval_eps_draws (the evaluation kernels' default heading and eps draw), rrt_stream (the planner's own U[0,1)).
+  Every stream is Philox4x32-10 keyed by the 64-bit seed; the counter's fourth word carries the stream's constant (STREAMS), which
+  keeps the streams apart (tests/test_oracle_philox.py::test_fourth_counter_word_separates_the_streams).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline may import this module.
 """
@@ -123,3 +129,148 @@ def act_draws(n: int, seed: int, counter: int, n_actions: int):
     u = ((r[:, 0] >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
     rnd = ((r[:, 1] * np.uint64(n_actions)) >> np.uint64(32)).astype(np.int64)
     return u, rnd
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The streams' counter words.  STREAMS: the constant in the counter's fourth word -- the domain separation.
+# ---------------------------------------------------------------------------------------------------------------------
+STREAMS = {"replay": 0x5A3B, "act": 0x0AC7, "randn": 0x6A55, "eval_noise": 0x5AC0, "per": 0x09E7, "reset": 0x5EED,
+           "eval_heading": 0xE7A1, "eval_eps": 0xE75F, "rrt": 0x7272}
+TWO_PI = 6.283185307179586                    # the f64 2 pi of random.uniform(0, 2 * pi)
+TWO_PI_F32 = np.float32(6.283185307179586)    # what an f32 kernel multiplies by: 6.2831855
+
+
+def _words(w0, w1, w2, w3):
+    """Counter words, each a scalar or an array, broadcast together -> (..., 4) uint64 holding 32-bit values."""
+    return np.stack(np.broadcast_arrays(*(np.asarray(w, dtype=np.uint64) & U32 for w in (w0, w1, w2, w3))), axis=-1)
+
+
+def _split(v: int):
+    return int(v) & 0xFFFFFFFF, (int(v) >> 32) & 0xFFFFFFFF
+
+
+def stream_counters(name: str, index, a: int = 0, b: int = 0):
+    """The counter words of stream `name` for element(s) `index`:
+      replay        (index, counter_lo, counter_hi, c)        a = the update's counter; index 0 and 1 give the six round keys
+      act, per      (index, counter_lo, counter_hi, c)        a = counter; index = agent / sample
+      reset         (index, tick_lo, tick_hi, c)              a = tick; index = agent
+      randn         (quad_lo, quad_hi, counter_lo, counter_hi ^ c)      a = counter; index = quad = element // 4
+      eval_noise, eval_eps      (episode, step, 0, c)         index = episode, a = step
+      eval_heading  (episode, 0, 0, c)
+      rrt           (k, scenario, attempt, c)                 index = k (the k-th uniform), a = scenario, b = attempt"""
+    c = STREAMS[name]
+    if name in ("replay", "act", "per", "reset"):
+        lo, hi = _split(a)
+        return _words(index, lo, hi, c)
+    if name == "randn":
+        lo, hi = _split(a)
+        q = np.asarray(index, dtype=np.uint64)
+        return _words(q, q >> np.uint64(32), lo, hi ^ c)
+    if name in ("eval_noise", "eval_eps"):
+        return _words(index, a, 0, c)
+    if name == "eval_heading":
+        return _words(index, 0, 0, c)
+    if name == "rrt":
+        return _words(index, a, b, c)
+    raise KeyError(name)
+
+
+def u53(a, b):
+    """CPython's random(): ((a >> 5) * 2^26 + (b >> 6)) * 2^-53 from two 32-bit words -> float64 in [0, 1).  Exact: the integer
+    has at most 53 bits."""
+    a = np.asarray(a, dtype=np.uint64) & U32
+    b = np.asarray(b, dtype=np.uint64) & U32
+    k = (a >> np.uint64(5)) * np.uint64(1 << 26) + (b >> np.uint64(6))
+    return k.astype(np.float64) * 2.0 ** -53
+
+
+class Normals:
+    """Box-Muller on 24-bit uniforms, element by element: u1 in (0, 1], u2 in [0, 1) and the angle t = fl32(fl32(2 pi) u2) are the
+    float32 values an f32 kernel holds (all three exact in numpy float32); rad = sqrt(-2 ln u1) and z = rad cos t (even
+    elements) / rad sin t (odd elements) are float64, evaluated AT those float32 inputs."""
+
+    def __init__(self, u1, u2, t, rad, z):
+        self.u1, self.u2, self.t, self.rad, self.z = u1, u2, t, rad, z
+
+
+def box_muller(w1, w2, *, shift: int = 8, plus: int = 1, two_pi=TWO_PI_F32):
+    """Words w1, w2 (same shape S) -> Normals of shape S + (2,): [..., 0] the cosine branch, [..., 1] the sine branch.
+    u1 = ((w1 >> 8) + 1) 2^-24, u2 = (w2 >> 8) 2^-24.  shift / plus / two_pi exist for the mutation tests only."""
+    w1 = np.asarray(w1, dtype=np.uint64) & U32
+    w2 = np.asarray(w2, dtype=np.uint64) & U32
+    s = np.float32(2.0 ** -24)
+    u1 = ((w1 >> np.uint64(shift)) + np.uint64(plus)).astype(np.float32) * s
+    u2 = (w2 >> np.uint64(shift)).astype(np.float32) * s
+    t = (two_pi * u2).astype(np.float32)               # f32 x f32 -> one f32 rounding; an f64 two_pi rounds the f64 product
+    with np.errstate(divide="ignore"):
+        rad = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
+    t64 = t.astype(np.float64)
+    z = np.stack([rad * np.cos(t64), rad * np.sin(t64)], axis=-1)
+    two = lambda x: np.stack([x, x], axis=-1)          # noqa: E731
+    return Normals(two(u1), two(u2), two(t), two(rad), z)
+
+
+def _flatten_pairs(parts, n):
+    """Normals of shape (quads, 2 pairs, 2 components) -> the first n elements in element order."""
+    return Normals(*(getattr(parts, k).reshape(-1)[:n] for k in ("u1", "u2", "t", "rad", "z")))
+
+
+def randn(n: int, seed: int, counter: int) -> Normals:
+    """uavenv_randn(seed, counter, n): elements 4q .. 4q + 3 come from the four words (x, y, z, w) of quad q's Philox block:
+    (x, y) -> ra cos, ra sin; (z, w) -> rb cos, rb sin."""
+    quads = (int(n) + 3) // 4
+    r = philox4x32_10(stream_counters("randn", np.arange(quads, dtype=np.uint64), counter), _key(seed))
+    return _flatten_pairs(box_muller(r[:, [0, 2]], r[:, [1, 3]]), n)
+
+
+def eval_noise(n: int, steps: int, seed: int) -> Normals:
+    """evaluate.sac_noise(n, steps, seed): arrays [n, steps, 2]; component 0 is the cosine branch, component 1 the sine branch of
+    the block of (episode, step)."""
+    e = np.arange(n, dtype=np.uint64)[:, None]
+    st = np.arange(steps, dtype=np.uint64)[None, :]
+    r = philox4x32_10(stream_counters("eval_noise", e, st), _key(seed))
+    return box_muller(r[..., 0], r[..., 1])
+
+
+def per_draws(batch: int, seed: int, counter: int, total: float) -> np.ndarray:
+    """The stratified draws of ReplayTree.sample (replay_buffer.py:147, :160-162) as uavenv_per_sample makes them without a
+    caller's stream: random.uniform(seg i, seg (i + 1)) = a + (b - a) random() with seg = int(total) / batch, pulled back onto
+    `total` (the library's clamp).  Plain float64, one rounding per operation."""
+    i = np.arange(batch, dtype=np.uint64)
+    r = philox4x32_10(stream_counters("per", i, counter), _key(seed))
+    seg = np.floor(np.float64(total)) / np.float64(batch)
+    a = seg * i.astype(np.float64)
+    b = seg * (i.astype(np.float64) + 1.0)
+    v = a + (b - a) * u53(r[:, 0], r[:, 1])
+    return np.minimum(v, np.float64(total))
+
+
+def reset_draws(n: int, seed: int, tick: int, m: int):
+    """UAV.reset() of agents 0..n-1 at `tick` from a bank of m scenarios -> (scn [n] int64, heading [n] float64): the scenario is
+    floor(z m / 2^32) from the block's third word, the heading random.uniform(0, 2 pi) = 2 pi u53(x, y)."""
+    r = philox4x32_10(stream_counters("reset", np.arange(n, dtype=np.uint64), tick), _key(seed))
+    scn = ((r[:, 2].astype(np.uint64) * np.uint64(m)) >> np.uint64(32)).astype(np.int64)
+    return scn, TWO_PI * u53(r[:, 0], r[:, 1])
+
+
+def eval_headings(n: int, seed: int) -> np.ndarray:
+    """The default initial heading of evaluation episodes 0..n-1 (v0 = None): 2 pi u53(x, y)."""
+    r = philox4x32_10(stream_counters("eval_heading", np.arange(n, dtype=np.uint64)), _key(seed))
+    return TWO_PI * u53(r[:, 0], r[:, 1])
+
+
+def eval_eps_draws(n: int, steps: int, seed: int, n_actions: int):
+    """-> (u [n, steps] float32 in [0, 1), random_action [n, steps]): step t of episode e takes random_action where u < eps
+    (strict), the greedy action otherwise."""
+    e = np.arange(n, dtype=np.uint64)[:, None]
+    st = np.arange(steps, dtype=np.uint64)[None, :]
+    r = philox4x32_10(stream_counters("eval_eps", e, st), _key(seed)).astype(np.uint64)
+    u = (r[..., 0] >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    rnd = ((r[..., 1] * np.uint64(n_actions)) >> np.uint64(32)).astype(np.int64)
+    return u, rnd
+
+
+def rrt_stream(seed: int, scenario: int, attempt: int, length: int) -> np.ndarray:
+    """The planner's own random() for (scenario, attempt): uniforms 0..length-1, u53 of the first two words of block k."""
+    r = philox4x32_10(stream_counters("rrt", np.arange(length, dtype=np.uint64), scenario, attempt), _key(seed))
+    return u53(r[:, 0], r[:, 1])

@@ -1,8 +1,16 @@
 """oracle/philox.py pinned: Random123's published known-answer vectors for philox4x32_10 (kat_vectors, Salmon et al.),
-and the structural properties the replay draw relies on (a permutation: distinct draws, full coverage)."""
+and the structural properties the replay draw relies on (a permutation: distinct draws, full coverage).
+
+The other streams' restatements (randn, eval_noise, per_draws, reset_draws, eval_headings, eval_eps_draws, rrt_stream) are what
+tests/test_random_streams_gpu.py holds the device to, value by value; here their own properties are pinned: u53's range, the
+standard-normal law of the Box-Muller streams (the distribution claim lives HERE -- the GPU tests compare numbers), the
+stratification of the prioritised draws, and the separation of the nine streams by the counter's fourth word."""
 import numpy as np
 
 from oracle import philox as px
+
+# the planner case of tests/test_random_streams_gpu.py: seed, rows, uniforms per row, and the lowered max_iter of its second case
+RRT_SEED, RRT_ROWS, RRT_LEN, RRT_MAX_ITER_LOW = (0x7272 << 32) | 11, 64, 6000, 84
 
 
 def test_philox4x32_10_known_answers():
@@ -70,3 +78,128 @@ def test_valid_only_draws_reject_over_the_permutation():
     f2, e2, fo2 = px.replay_draws_valid(filled * n_envs, 1, U, 0, valid, 8, 5, 2, head, filled, frames, n_envs)
     fs, es = px.replay_draws(filled * n_envs, 5, 2, head, filled, frames, n_envs)
     assert (f2 == fs).all() and (e2 == es).all()                       # no second position exists: every draw keeps its first row
+
+
+def test_u53_range_and_monotonicity():
+    assert px.u53(0, 0) == 0.0
+    assert px.u53(2 ** 32 - 1, 2 ** 32 - 1) == 1.0 - 2.0 ** -53
+    assert px.u53(31, 63) == 0.0 and px.u53(32, 0) == 2.0 ** -27 and px.u53(0, 64) == 2.0 ** -53     # the low 5 / 6 bits are dropped
+    a = np.sort(np.random.default_rng(0).integers(0, 2 ** 32, 4096, dtype=np.uint64))
+    for b in (0, 12345, 2 ** 32 - 1):
+        u = px.u53(a, b)
+        assert (np.diff(u) >= 0).all() and u.min() >= 0.0 and u.max() < 1.0                          # monotone in a
+        assert ((np.diff(u) > 0) == (np.diff(a >> np.uint64(5)) > 0)).all()                          # strictly, per 32 values of a
+
+
+def _standard_normal(z, lanes):
+    from scipy import stats
+    z = z.reshape(-1)
+    assert stats.kstest(z, "norm").pvalue > 1e-4
+    for k in range(lanes):
+        assert stats.kstest(z[k::lanes], "norm").pvalue > 1e-4, k
+    assert abs(np.corrcoef(z[0::2], z[1::2])[0, 1]) < 0.01                                           # cosine against sine branch
+    assert np.abs(z).max() <= np.sqrt(48.0 * np.log(2.0))
+
+
+def test_randn_and_eval_noise_are_standard_normal():
+    n = 1 << 20
+    g = px.randn(n, seed=(7 << 32) | 11, counter=(3 << 32) | 5)
+    _standard_normal(g.z, 4)
+    assert g.u1.dtype == np.float32 and g.u2.dtype == np.float32 and g.t.dtype == np.float32
+    assert g.u1.min() > 0.0 and g.u1.max() <= 1.0 and g.u2.min() >= 0.0 and g.u2.max() < 1.0
+    assert np.array_equal(g.t, (px.TWO_PI_F32 * g.u2).astype(np.float32)) and float(px.TWO_PI_F32) == 6.2831854820251465
+    assert abs(np.corrcoef(g.z[0::4], g.z[2::4])[0, 1]) < 0.01                                       # the two pairs of a quad
+    e = px.eval_noise(1 << 12, 1 << 7, seed=(9 << 32) | 2)                                           # 2^19 blocks, 2^20 values
+    assert e.z.shape == (1 << 12, 1 << 7, 2)
+    _standard_normal(e.z, 2)
+    # a shorter request is a prefix; another counter / seed is another stream, also where only the high halves differ
+    assert np.array_equal(px.randn(1027, 5, 9).z, px.randn(4099, 5, 9).z[:1027])
+    for other in (px.randn(64, 5, 9 + (1 << 32)), px.randn(64, 5 + (1 << 32), 9), px.randn(64, 5, 10)):
+        assert not np.array_equal(other.z, px.randn(64, 5, 9).z)
+
+
+def test_box_muller_extreme_value():
+    """rad is largest at the smallest u1 = 2^-24 (first word < 256): sqrt(-2 ln 2^-24) = sqrt(48 ln 2) = 5.768..., and nowhere else."""
+    top = np.sqrt(48.0 * np.log(2.0))
+    lo = px.box_muller(np.array([0, 255, 256, 2 ** 32 - 1]), np.array([0, 0, 0, 0]))
+    assert lo.u1[0, 0] == np.float32(2.0 ** -24) and lo.u1[1, 0] == lo.u1[0, 0] and lo.u1[2, 0] == np.float32(2.0 ** -23)
+    assert lo.rad[0, 0] == top and lo.rad[1, 0] == top and lo.rad[2, 0] < top
+    assert lo.u1[3, 0] == 1.0 and lo.rad[3, 0] == 0.0 and lo.z[0, 0] == top and lo.z[0, 1] == 0.0     # u2 = 0: cos 1, sin 0
+    hi = px.box_muller(np.array([0]), np.array([2 ** 32 - 1]))
+    assert hi.u2[0, 0] == np.float32(1.0 - 2.0 ** -24) and hi.t[0, 0] < px.TWO_PI_F32
+
+
+def test_per_draws_are_stratified_and_clamped():
+    for batch, total in ((1, 0.5), (3, 7.25), (256, 1000.75), (1000, 12345.0)):
+        v = px.per_draws(batch, seed=(4 << 32) | 1, counter=(2 << 32) | 3, total=total)
+        seg = np.floor(total) / batch
+        i = np.arange(batch)
+        assert v.dtype == np.float64 and (v >= seg * i).all() and (v <= seg * (i + 1)).all() and (v <= total).all()
+    assert (px.per_draws(8, 1, 0, 0.25) == 0.0).all()                                               # int(total) = 0: every draw is 0
+    assert not np.array_equal(px.per_draws(64, 1, 5, 99.0), px.per_draws(64, 1, 5 + (1 << 32), 99.0))
+
+
+def test_reset_eval_and_planner_draws_ranges():
+    for m in (1, 3, 1000):
+        scn, h = px.reset_draws(4096, seed=(1 << 40) | 7, tick=(1 << 33) | 2, m=m)
+        assert scn.min() >= 0 and scn.max() < m and len(np.unique(scn)) >= 0.95 * m    # (1000 rows: e^-4.096 = 1.7 % unseen)
+        assert h.min() >= 0.0 and h.max() < px.TWO_PI
+    assert not np.array_equal(px.reset_draws(64, 3, 5, 1000)[0], px.reset_draws(64, 3, 5 + (1 << 32), 1000)[0])
+    h = px.eval_headings(4096, seed=5)
+    assert h.min() >= 0.0 and h.max() < px.TWO_PI and abs(h.mean() - np.pi) < 0.1
+    u, r = px.eval_eps_draws(512, 8, seed=5, n_actions=3)
+    assert u.dtype == np.float32 and u.shape == (512, 8) and u.min() >= 0.0 and u.max() < 1.0
+    assert set(np.unique(r).tolist()) == {0, 1, 2}
+    s = px.rrt_stream(seed=11, scenario=3, attempt=0, length=4096)
+    assert s.min() >= 0.0 and s.max() < 1.0 and abs(s.mean() - 0.5) < 0.03
+    assert not np.array_equal(s, px.rrt_stream(11, 3, 1, 4096)) and not np.array_equal(s, px.rrt_stream(11, 4, 0, 4096))
+
+
+def test_fourth_counter_word_separates_the_streams():
+    """For counters / ticks below 2^32 the fourth counter word of every stream is its own constant: no two streams of one seed can
+    ever share a Philox block.  Above 2^32 seven of the nine keep it (their high half sits in the third word or is absent); randn
+    xors its constant INTO the counter's high half, so there it can take another stream's value.  The one aliasing that exists:
+    randn at counter_hi == 0x6a55 ^ 0x0ac7 has the act stream's fourth word, and its quad q (< 2^32) then reads the block of
+    act_draws(index q, counter = counter_lo << 32) -- first word and all."""
+    idx = np.arange(5, dtype=np.uint64)
+    small = 0xFFFFFFFF
+    consts = {}
+    for name in px.STREAMS:
+        w = px.stream_counters(name, idx, small, 3)
+        assert w.shape == (5, 4) and len(set(w[:, 3].tolist())) == 1
+        consts[name] = int(w[0, 3])
+    assert consts == px.STREAMS and len(set(consts.values())) == len(px.STREAMS) == 9
+    big = (0x1234 << 32) | 9
+    for name in px.STREAMS:
+        w3 = int(px.stream_counters(name, idx, big, 3)[0, 3])
+        assert w3 == (px.STREAMS[name] ^ 0x1234 if name == "randn" else px.STREAMS[name])
+    # the aliasing, in numbers: u1 of randn's element 4 q is the act stream's u plus 2^-24
+    c_lo = 0x00C0FFEE
+    g = px.randn(4 * 64, seed=77, counter=((0x6A55 ^ 0x0AC7) << 32) | c_lo)
+    u, _ = px.act_draws(64, seed=77, counter=c_lo << 32, n_actions=3)
+    assert np.array_equal(g.u1[0::4], u + np.float32(2.0 ** -24))
+    g2 = px.randn(4 * 64, seed=77, counter=c_lo)
+    assert not np.array_equal(g2.u1[0::4], u + np.float32(2.0 ** -24))
+
+
+def test_oracle_planner_stays_inside_the_stream_on_the_restated_draws():
+    """The GPU test of the planner's stream leaves out rows whose plan does not fit (2 <= nodes <= K = 64) or that may have run past
+    the RRT_LEN uniforms handed to the stream-fed mode, and allows at most 1/8 of them: the CPU planner on the same restated stream
+    must stay inside that cap by itself (it plans 64 of 64).  With max_iter lowered some first attempts fail and fit on the
+    attempt-1 stream: the second GPU case is not empty."""
+    from conftest import load_golden
+    from oracle import pyoracle as po
+    world = po.OracleWorld(load_golden("world_stock.npz")["buildings"])
+
+    def plan(u, max_iter):
+        # UAV.reset: the heading draw first, then start (x, y) and goal (x, y) by random.uniform, then the planner's own draws
+        start = [10.0 + (210.0 - 10.0) * u[1], 1.0 + (10.0 - 1.0) * u[2], 0.0]
+        goal = [330.0 + (490.0 - 330.0) * u[3], 420.0 + (490.0 - 420.0) * u[4], 0.0]
+        path, it = po.rrt_get_path(world, po.OracleRng(0).replay(u[5:]), start, goal, max_iter=max_iter)
+        return path is not None and 2 <= len(path) <= 64 and 5 + 4 * it <= RRT_LEN
+
+    fit = sum(plan(px.rrt_stream(RRT_SEED, r, 0, RRT_LEN), 10000) for r in range(RRT_ROWS))
+    assert fit >= RRT_ROWS - RRT_ROWS // 8, fit
+    second = sum(not plan(px.rrt_stream(RRT_SEED, r, 0, RRT_LEN), RRT_MAX_ITER_LOW) and plan(px.rrt_stream(RRT_SEED, r, 1, RRT_LEN), RRT_MAX_ITER_LOW)
+                 for r in range(RRT_ROWS))
+    assert second >= 8, second
