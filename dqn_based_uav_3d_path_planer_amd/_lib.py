@@ -403,6 +403,13 @@ def load() -> C.CDLL:
     lib.uavenv_dqn_reduce_adam.argtypes = [net, vp, i32, f32, f32, f32, f32, i32, i32, vp, vp, vp]
     lib.uavenv_dqn_reduce_adam_gated.restype = C.c_int
     lib.uavenv_dqn_reduce_adam_gated.argtypes = [net, vp, i32, f32, f32, f32, f32, i32, i32, vp, vp, vp, C.c_uint32, vp]
+    # (csrc/dqn_internal.hpp as well: the three Adam launches that keep the layer-1 image current)
+    lib.uavenv_dqn_adam_img.restype = C.c_int
+    lib.uavenv_dqn_adam_img.argtypes = [net, vp, f32, f32, f32, f32, i32, i32, vp, vp, vp]
+    lib.uavenv_dqn_reduce_adam_img.restype = C.c_int
+    lib.uavenv_dqn_reduce_adam_img.argtypes = [net, vp, i32, f32, f32, f32, f32, i32, i32, vp, vp, vp, C.c_uint32, vp, vp]
+    lib.uavenv_dqn_adam_p2p_img.restype = C.c_int
+    lib.uavenv_dqn_adam_p2p_img.argtypes = [net, vp, f32, f32, f32, f32, i32, i32, vp, vp, vp, vp]
     lib.uavenv_dqn_act.restype = C.c_int
     lib.uavenv_dqn_act.argtypes = [net, vp, i32, i32, f32, u64, u64, vp, vp, vp, vp]
     per, f64 = C.POINTER(UavPer), C.c_double

@@ -93,6 +93,11 @@ __device__ uint32_t p2p_wait_once(const P2PDev &d, unsigned char *mine, int P_ch
     uint32_t *verdict = reinterpret_cast<uint32_t *>(mine + (size_t)kMaxWorld * 64);
     const uint32_t tag = d.seq << 2;
     if (blockIdx.x != 0) {
+        // The sticky word first: a pull behind a REFUSED push (uavenv_dqn_reduce_p2p returns UAVENV_EP2P and uses no sequence
+        // number) carries the sequence number of the last pull, whose healthy verdict is still in the verdict word -- taken from
+        // there, every workgroup but the first stepped its parameters with that pull's sums once more.
+        const uint32_t sticky = __hip_atomic_load(d.errors + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (sticky) return sticky;
         // twice workgroup 0's own worst case (world waits of spin_limit polls each), in 64 bits -- 2 * 2^27 * 16 wrapped a
         // uint32 to ~1 k polls and raised a spurious sticky timeout -- and at workgroup 0's poll interval
         const unsigned long long bound = 2ull * (unsigned long long)d.spin_limit * (unsigned long long)d.world + 1024ull;

@@ -382,8 +382,8 @@ class FusedDQNLearner:
     # -- multi-GPU: the gradient bucket summed over peer-mapped HBM instead of a collective call -------------------
     def enable_p2p(self, verify: bool = True, check_every: int = 256, spin_limit: int = 0) -> bool:
         """Set up csrc/p2p.hip between the ranks of the initialised process group (one rank per GPU of ONE node): every
-        rank maps every other rank's receive area through HIP IPC.  With verify, one all-reduce of a known vector is
-        compared with torch.distributed's result on every rank; on any failure (IPC not available, timeout, mismatch)
+        rank maps every other rank's receive area through HIP IPC.  With verify, four exchanges of payloads every rank can
+        regenerate are compared with their locally computed sum on every rank; on any failure (IPC not available, timeout, mismatch)
         the learner keeps the RCCL path.  Returns whether the peer-to-peer path is active on ALL ranks.
         check_every: the ranks compare a checksum of their weights on the device every that many updates (0 = never);
         spin_limit: polls before a flag wait gives up (0 = the library's default, about a second)."""
@@ -399,7 +399,7 @@ class FusedDQNLearner:
         if ok and verify:
             # Round 6: the exchange has never crossed a link on this build's boxes, so it is not accepted on one
             # tidy vector.  FOUR exchanges back to back -- both receive slots, twice each -- of a multi-KB payload that is random per
-            # rank and per iteration, each compared on every rank with torch.distributed's all-reduce of the same payload.
+            # rank and per iteration, each compared on every rank with the sum of ALL ranks' payloads, regenerated locally (below).
             import time as _time
             n = self.lib.uavenv_dqn_partial_rows(64)
             stride = self.lib.uavenv_dqn_partial_stride(C.byref(self.net))
