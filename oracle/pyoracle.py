@@ -87,6 +87,8 @@ def _load(name: str) -> C.CDLL:
     lib.orc_rrt_get_path.restype = C.c_int
     lib.orc_rrt_get_path.argtypes = [C.POINTER(World), C.POINTER(Rng), d, C.c_int, d, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.orc_rrt_get_path_n.restype = C.c_int
+    lib.orc_rrt_get_path_n.argtypes = lib.orc_rrt_get_path.argtypes + [C.c_int, C.POINTER(C.c_int)]
     lib.orc_step_many.restype = None
     lib.orc_step_many.argtypes = [C.POINTER(World), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int]
@@ -213,15 +215,23 @@ class OracleRng:
 
 
 def rrt_get_path(world: "OracleWorld", rng: "OracleRng", start, goal, step_size=30.0, max_iter=10000, obstacle_step=5.0,
-                 cap=KMAX):
-    """PathPlan/RRT.py:63-105 -> (path [n,3], iterations)."""
+                 cap=KMAX, max_nodes=None, want_nodes=False):
+    """PathPlan/RRT.py:63-105 -> (path [n,3], iterations).  max_nodes: the GPU planner's cap on the tree (the loop runs
+    while it < max_iter and nodes < max_nodes; None: the reference, no cap); want_nodes: -> (path, iterations, nodes in
+    the tree).  path is None where it does not fit cap."""
     s = np.ascontiguousarray(start, dtype=np.float64)
     g = np.ascontiguousarray(goal, dtype=np.float64)
     out = np.zeros((cap, 3))
-    it = C.c_int(0)
-    n = world.lib.orc_rrt_get_path(C.byref(world.w), C.byref(rng.r), float(step_size), int(max_iter), float(obstacle_step),
-                                   s.ctypes.data, g.ctypes.data, out.ctypes.data, cap, C.byref(it))
-    return (out[:n].copy() if n >= 0 else None), it.value
+    it, nn = C.c_int(0), C.c_int(0)
+    if max_nodes is None and not want_nodes:
+        n = world.lib.orc_rrt_get_path(C.byref(world.w), C.byref(rng.r), float(step_size), int(max_iter), float(obstacle_step),
+                                       s.ctypes.data, g.ctypes.data, out.ctypes.data, cap, C.byref(it))
+    else:
+        n = world.lib.orc_rrt_get_path_n(C.byref(world.w), C.byref(rng.r), float(step_size), int(max_iter),
+                                         float(obstacle_step), s.ctypes.data, g.ctypes.data, out.ctypes.data, cap,
+                                         C.byref(it), 0 if max_nodes is None else int(max_nodes), C.byref(nn))
+    path = out[:n].copy() if n >= 0 else None
+    return (path, it.value, nn.value) if want_nodes else (path, it.value)
 
 
 class OracleBatch:

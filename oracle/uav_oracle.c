@@ -403,10 +403,14 @@ static int rrt_obstacle_free(const orc_world *w, const double a[3], const double
     return 1;
 }
 
-/* RRT.py:63-105 */
-int orc_rrt_get_path(const orc_world *w, orc_rng *r, double step_size, int max_iter, double obstacle_step,
-                     const double start[3], const double goal[3], double *path_xyz, int cap, int *n_iters)
+/* RRT.py:63-105, with the GPU planner's node cap (csrc/rrt.hip: the iteration loop also stops once the tree holds
+ * max_nodes nodes; the reference has no such cap: max_nodes <= 0 or > max_iter + 1 never binds).  *n_nodes: the size
+ * of the tree when the loop ended, the start node included. */
+int orc_rrt_get_path_n(const orc_world *w, orc_rng *r, double step_size, int max_iter, double obstacle_step,
+                       const double start[3], const double goal[3], double *path_xyz, int cap, int *n_iters,
+                       int max_nodes, int *n_nodes)
 {
+    if (max_nodes <= 0 || max_nodes > max_iter + 2) max_nodes = max_iter + 2;
     rrt_node *nodes = (rrt_node *)malloc(sizeof(rrt_node) * (size_t)(max_iter + 2));
     int nn = 0;
     nodes[nn].x = start[0]; nodes[nn].y = start[1]; nodes[nn].z = start[2];
@@ -414,7 +418,7 @@ int orc_rrt_get_path(const orc_world *w, orc_rng *r, double step_size, int max_i
     int goal_parent = -1;
     double goal_radius = step_size;
     int it;
-    for (it = 0; it < max_iter; ++it) {
+    for (it = 0; it < max_iter && nn < max_nodes; ++it) {
         /* get_random_point :26-34 */
         double rp[3];
         if (orc_rng_uniform(r, 0, 1) > 0.5) {
@@ -468,6 +472,7 @@ int orc_rrt_get_path(const orc_world *w, orc_rng *r, double step_size, int max_i
         }
     }
     if (n_iters) *n_iters = it;
+    if (n_nodes) *n_nodes = nn;
     /* path :96-103 : goal, then parents back to the start, reversed */
     int count = 1;
     for (int p = goal_parent; p >= 0; p = nodes[p].parent) count++;
@@ -480,6 +485,13 @@ int orc_rrt_get_path(const orc_world *w, orc_rng *r, double step_size, int max_i
     }
     free(nodes);
     return count;
+}
+
+/* RRT.py:63-105 */
+int orc_rrt_get_path(const orc_world *w, orc_rng *r, double step_size, int max_iter, double obstacle_step,
+                     const double start[3], const double goal[3], double *path_xyz, int cap, int *n_iters)
+{
+    return orc_rrt_get_path_n(w, r, step_size, max_iter, obstacle_step, start, goal, path_xyz, cap, n_iters, 0, 0);
 }
 
 /* Agents/UAV.py:327-366 (global reset) */

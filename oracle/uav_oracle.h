@@ -104,6 +104,11 @@ double orc_rng_uniform(orc_rng *r, double a, double b);/* random.uniform(a,b) */
 /* PathPlan/RRT.py:63-105; returns the number of path nodes written (<= cap), or -needed if cap too small */
 int orc_rrt_get_path(const orc_world *w, orc_rng *r, double step_size, int max_iter, double obstacle_step,
                      const double start[3], const double goal[3], double *path_xyz, int cap, int *n_iters);
+/* the same planner with the GPU planner's rule "it < max_iter && nodes < max_nodes" (max_nodes <= 0: no cap) and the
+ * size of the tree reported */
+int orc_rrt_get_path_n(const orc_world *w, orc_rng *r, double step_size, int max_iter, double obstacle_step,
+                       const double start[3], const double goal[3], double *path_xyz, int cap, int *n_iters,
+                       int max_nodes, int *n_nodes);
 void orc_reset(const orc_world *w, orc_uav *u, orc_rng *r, double sub_granularity); /* UAV.py:327-366 */
 
 /* ---- batched helpers (CPU baseline; OpenMP over independent agents) ---- */
