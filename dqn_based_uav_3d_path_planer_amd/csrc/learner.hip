@@ -719,7 +719,8 @@ __global__ void __launch_bounds__(256) k_dqn_grad_packed(Grad2Args ga)
 // w & 3, wavefronts 4..7 (group 1) own the bootstrap value of the same strip -- q_target(s') (and q_local(s') for the
 // double-DQN action choice) -- and hand it over as ONE float per sample; the two groups run concurrently, each SIMD
 // interleaving a group-0 and a group-1 wavefront.  Both groups stage weights (group 0 the local fc1, group 1 the target
-// fc1) and share the weight-gradient products (group 0: k-column tiles 0, 2, 4, 6; group 1: tiles 1, 3, 5 and dW2).
+// fc1) and share the weight-gradient products (group 1: the flag columns on the f16 matrix pipe; group 0: the scalar columns and
+// dW2 on the f32 pipe -- see grad_products_split8).
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void w_issue_half(floatx4 (&v)[kStageIters], const float *W, int t256)
 {
@@ -732,99 +733,11 @@ __device__ __forceinline__ void w_issue_half(floatx4 (&v)[kStageIters], const fl
 }
 
 struct GradAcc8 {
-    floatx4 acc[6];                  // group 0: dW1^T k-column tiles 0, 2, 4, 6; group 1: tiles 1, 3, 5 and the dW2^T tile
-                                     // (form B of the split products: group 1 all six flag tiles, group 0 the gathered tile and dW2^T)
+    floatx4 acc[6];                  // group 1: the six flag tiles of dW1^T; group 0: acc[0] the gathered tile, acc[1] the dW2^T tile
     float csum[6];                   // group 0: column sums of dout (NMAX = 4), loss sum, valid count of its strips
 };
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Round 5: the weight-gradient products of k_dqn_grad_packed8 in the SPLIT form.
-//   dW1^T[c][j] = sum_s X[s][c] dH[s][j] over the tile's 64 samples.  80 of the 100 columns of X are 0 / 1 flags -- exact in f16 --
-//   so for them the product runs on v_mfma_f32_16x16x32_f16 with dH as TWO f16 terms, hi = f16(dH 2^S) and mid = f16((dH 2^S - hi)
-//   2^11, met by flags worth 2^-11 so that both terms share one accumulator) (22-23 significant bits relative to the tile's largest |dH|; 2^S, a power of two taken from that maximum, puts it at
-//   2^13..2^14: no overflow whatever the loss does, and the scaling is exact): every product is exact, the sums are f32.  The 15
-//   scalar columns (0..10, 86..89) and the ones column (-> db1) form ONE gathered 16-column tile on v_mfma_f32_16x16x4_f32 with the
-//   unscaled f32 dH, as before; the scalar columns' bits are 0 in the packed words, so the f16 products leave exact zeros there.
-//   Per wavefront: 12 f16 MFMAs (16 cycles) + 16 f32 MFMAs (32 cycles) instead of 64 f32 MFMAs -- 1.4 k matrix cycles per SIMD
-//   and tile instead of 4.1 k.
-// K (= sample) index of a lane group: sample(q, g, i) = 32 q + 16 (i >> 2) + 4 g + (i & 3) for f16 step q, K element i of lane
-// group g -- lane groups 4 samples apart are 16 LDS banks apart in the hidden tiles (kLh = 68) and in the packed rows (20 dwords);
-// f32 step kk = 8 q + i takes the same sample, so the lane's sixteen dH values serve both products.
-// Register layout out (the partial-row writer of the split kernel knows it): group 0: acc[0..2] = column tiles 0, 2, 4 (rows
-// 16 u + 4 g + e), acc[3] = the gathered tile (entry 4 g + e: columns 0..10 | 86..89 | ones); group 1: acc[0..2] = tiles 1, 3, 5,
-// acc[3] = dW2^T as before.
-// ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void grad_products_split8(const GradLdsP &L, const float *amax4, int grp, int strip, int r, int gq,
-                                                     GradAcc8 &A)
-{
-    // ---- the tile's scale (qnet_device.hpp: split_scale)
-    float up, down;
-    split_scale(fmaxf(fmaxf(amax4[0], amax4[1]), fmaxf(amax4[2], amax4[3])), up, down);
-    // ---- every operand of the phase is requested first (one wavefront's dependent LDS round trips are not hidden by anything)
-    const uint32_t *pr = L.Ps + 4 * gq * kPackedDwords;
-    const float *db = L.dHs + 4 * gq * kLh + 16 * strip + r;
-    uintx4 mk[2][8];
-    float dh[2][8], a32[2][8], b32[2][8] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
-    // group 0: A of the f32 product = entry r of the gathered tile: packed dword 4 + r (columns 0..10), 15 + (r - 11) (86..89); entry
-    // 15 is the ones column (dword 19 is a zero pad: replaced below).  group 1: A = H[s][16 strip + r], B = dout[s][r]
-    const int dsc = r < 15 ? 4 + r : 19;
-    const float *ha = L.Hs + 4 * gq * kLh + 16 * strip + r;
-    const float *ob = L.douts + 4 * gq * kMaxOut + r;
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int s1 = 32 * q + 16 * (i >> 2) + (i & 3);           // + 4 gq through the base pointers
-            mk[q][i] = *reinterpret_cast<const uintx4 *>(pr + s1 * kPackedDwords);
-            dh[q][i] = db[s1 * kLh];
-            if (grp == 0) {
-                a32[q][i] = __uint_as_float(pr[s1 * kPackedDwords + dsc]);
-            } else {
-                a32[q][i] = ha[s1 * kLh];
-                b32[q][i] = ob[s1 * kMaxOut];
-            }
-        }
-    // ---- B of the f16 products: the lane's sixteen dH values, scaled and split
-    half8 bh[2], bm[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) split_half8(dh[q], up, bh[q], bm[q]);
-    // ---- the flag columns: tiles u = 2 v + grp, v = 0..2 (columns 16 u + r: word u >> 1, bit 16 (u & 1) + r of the row's flag words)
-    floatx4 ch[3];
-#pragma unroll
-    for (int v = 0; v < 3; ++v) ch[v] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-    const uint32_t sh = (uint32_t)(grp == 0 ? r : 16 + r);            // u & 1 == grp
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        half8 a1[3], at[3];
-#pragma unroll
-        for (int v = 0; v < 3; ++v) flags_to_half8(mk[q], v, sh, a1[v], at[v]);                  // u >> 1 == v
-#pragma unroll
-        for (int v = 0; v < 3; ++v) ch[v] = mfma16h(a1[v], bh[q], ch[v]);
-#pragma unroll
-        for (int v = 0; v < 3; ++v) ch[v] = mfma16h(at[v], bm[q], ch[v]);      // (mid x 2^-11: same accumulator, three MFMAs later)
-    }
-    // ---- the f32 product: group 0 the gathered scalar tile x dH, group 1 H x dout (dW2^T)
-    floatx4 c32 = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-    const bool ones = grp == 0 && r == 15;
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            c32 = mfma16(ones ? 1.0f : a32[q][i], grp == 0 ? dh[q][i] : b32[q][i], c32);
-    // ---- into the persistent accumulators: (hi + mid 2^-11) 2^-S, exact scalings
-#pragma unroll
-    for (int v = 0; v < 3; ++v)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) A.acc[v][k] += ch[v][k] * down;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) A.acc[3][k] += c32[k];
-}
-
-// Form B of the split products (SPLIT == 2): the two groups' work is not symmetric -- group 0 carries the TD target and dL/dH while
-// group 1 waits -- so group 1 takes ALL six flag tiles and builds their A operands (the flag bits of every sample: they depend on the
-// packed rows only) while group 0 is still in td_backward; behind the barrier group 1 has 24 f16 MFMAs + the split of its sixteen dH
-// values left, group 0 the two f32 products (the gathered scalar tile x dH, H x dout).  Same operands in the same K order per
-// accumulator as form A: bit-identical results.
+// group 1's A operands of the six flag tiles, built ahead of the products (grad_products_split8)
 struct FlagOps {
     half8 one[2][6];                 // (the 2^-11 operand of the mid term is derived from it behind the barrier: two instructions per dword)
 };
@@ -850,8 +763,27 @@ __device__ __forceinline__ void flag_ops_build(const GradLdsP &L, int r, int gq,
         }
     }
 }
-__device__ __forceinline__ void grad_products_split8b(const GradLdsP &L, const float *amax4, int grp, int strip, int r, int gq,
-                                                      const FlagOps &F, GradAcc8 &A)
+// ---------------------------------------------------------------------------------------------------------------------
+// The weight-gradient products of k_dqn_grad_packed8 (HISTORY section 3.2).
+//   dW1^T[c][j] = sum_s X[s][c] dH[s][j] over the tile's 64 samples.  80 of the 100 columns of X are 0 / 1 flags -- exact in f16 --
+//   so for them the product runs on v_mfma_f32_16x16x32_f16 with dH as TWO f16 terms, hi = f16(dH 2^S) and mid = f16((dH 2^S - hi)
+//   2^11, met by flags worth 2^-11 so that both terms share one accumulator) (22-23 significant bits relative to the tile's largest
+//   |dH|; 2^S, a power of two taken from that maximum, puts it at 2^13..2^14: no overflow whatever the loss does, and the scaling
+//   is exact): every product is exact, the sums are f32.  The 15 scalar columns (0..10, 86..89) and the ones column (-> db1) form
+//   ONE gathered 16-column tile on v_mfma_f32_16x16x4_f32 with the unscaled f32 dH; the scalar columns' bits are 0 in the packed
+//   words, so the f16 products leave exact zeros there.
+// K (= sample) index of a lane group: sample(q, g, i) = 32 q + 16 (i >> 2) + 4 g + (i & 3) for f16 step q, K element i of lane
+// group g -- lane groups 4 samples apart are 16 LDS banks apart in the hidden tiles (kLh = 68) and in the packed rows (20 dwords);
+// f32 step kk = 8 q + i takes the same sample, so the lane's sixteen dH values serve both products.
+// The two groups' work ahead of the products is not symmetric -- group 0 carries the TD target and dL/dH while group 1 waits -- so
+// group 1 takes ALL six flag tiles and builds their A operands (flag_ops_build: the flag bits of every sample, which depend on the
+// packed rows only) while group 0 is still in td_backward; behind the barrier group 1 has 24 f16 MFMAs + the split of its sixteen
+// dH values left, group 0 the two f32 products (the gathered scalar tile x dH, H x dout): 32 f32 MFMAs.
+// Register layout out (the partial-row writer of k_dqn_grad_packed8 knows it): group 1: acc[u] = flag tile u (rows 16 u + 4 g + e);
+// group 0: acc[0] = the gathered tile (entry 4 g + e: columns 0..10 | 86..89 | ones), acc[1] = dW2^T.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void grad_products_split8(const GradLdsP &L, const float *amax4, int grp, int strip, int r, int gq,
+                                                     const FlagOps &F, GradAcc8 &A)
 {
     const float *db = L.dHs + 4 * gq * kLh + 16 * strip + r;
     float dh[2][8];
@@ -909,10 +841,9 @@ __device__ __forceinline__ void grad_products_split8b(const GradLdsP &L, const f
     for (int k = 0; k < 4; ++k) { A.acc[0][k] += csc[k]; A.acc[1][k] += cw2[k]; }
 }
 
-// SPLIT (round 5): the weight-gradient products in the split form -- see grad_products_split8 below.
 // GLDS (needs g.img): both layer-1 images come in by LDS-DMA (img_glds) -- the same bytes without the 28 staging registers per thread
 // and the ds_write pass; the staging barrier waits for them.
-template <bool FIRST, int SPLIT, bool GLDS>
+template <bool FIRST, bool GLDS>
 __device__ __forceinline__ void grad_tile_packed8(const GradArgs &g, const GradLdsP &L, float *qn_lds, int tile, bool more,
                                                   GradAcc8 &A)
 {
@@ -1013,7 +944,7 @@ __device__ __forceinline__ void grad_tile_packed8(const GradArgs &g, const GradL
     __syncthreads();                                  // bootstrap values handed over
     L_STAMP(3);
     FlagOps FO;
-    if (SPLIT == 2 && grp == 1) flag_ops_build(L, r, gq, FO);        // (while group 0 is in td_backward)
+    if (grp == 1) flag_ops_build(L, r, gq, FO);        // (while group 0 is in td_backward)
     if (grp == 0) {
         GradAcc<NMAX> T;                              // td_backward's accumulator interface: only csum is used here
 #pragma unroll
@@ -1022,73 +953,19 @@ __device__ __forceinline__ void grad_tile_packed8(const GradArgs &g, const GradL
         const float p_done = (float)raw_done, p_valid = (float)raw_valid;
         td_backward<NMAX>(g, L.W2l, hl, Fl, ql, qn_lds[strip * 16 + r], p_act, p_rew, p_done, p_valid, p_w, smp, T,
                           L.Hs + (strip * 16 + r) * kLh, L.dHs + (strip * 16 + r) * kLh, L.douts + (strip * 16 + r) * kMaxOut,
-                          SPLIT ? &amax : nullptr);
+                          &amax);
 #pragma unroll
         for (int a = 0; a < NMAX + 2; ++a) A.csum[a] = T.csum[a];
-        if (SPLIT) {                                  // max |dL/dH| of this strip: the tile's f16 scale is derived from the four
-            amax = wave_max64(amax);
-            if (lane == 0) qn_lds[kTile + strip] = amax;
-        }
+        amax = wave_max64(amax);                      // max |dL/dH| of this strip: the tile's f16 scale is derived from the four
+        if (lane == 0) qn_lds[kTile + strip] = amax;
     }
     __syncthreads();                                  // H, dH, dout and the packed s rows of all 64 samples visible
     L_STAMP(4);
-    if (SPLIT) {
-        if (SPLIT == 2) grad_products_split8b(L, qn_lds + kTile, grp, strip, r, gq, FO, A);
-        else grad_products_split8(L, qn_lds + kTile, grp, strip, r, gq, A);
-        if (more) __syncthreads();
-        return;
-    }
-    // ---- weight gradients over the 64 samples (MFMA step kk, lane group gq: sample (kk & 3) + 16 (kk >> 2) + 4 gq);
-    // hidden units 16 strip + r; group 0: X columns 16 u + r for u = 0, 2, 4, 6; group 1: u = 1, 3, 5, and dW2^T
-    {
-        const uint32_t *pr = L.Ps + 4 * gq * kPackedDwords;
-        const int ia = 4 + (r < 11 ? r : 10), ib = 15 + (r < 6 ? 0 : (r > 9 ? 3 : r - 6));
-        const bool sc0 = r < 11, sc5 = r >= 6 && r <= 9;
-        const float ones = r == 4 ? 1.0f : 0.0f;
-        const int sh = grp == 0 ? r : 16 + r;
-        const float *db = L.dHs + 4 * gq * kLh + 16 * strip + r;
-        const float *ha = L.Hs + 4 * gq * kLh + 16 * strip + r;
-        const float *ob = L.douts + 4 * gq * kMaxOut + r;
-        struct Raw { uintx4 mk; float sx, bdh, ah, bo; };
-        auto load = [&](int k) {
-            const int s1 = (k & 3) + 16 * (k >> 2);
-            Raw w;
-            w.mk = *reinterpret_cast<const uintx4 *>(pr + s1 * kPackedDwords);
-            w.sx = __uint_as_float(pr[s1 * kPackedDwords + (grp == 0 ? ia : ib)]);
-            w.bdh = db[s1 * kLh];
-            w.ah = ha[s1 * kLh];
-            w.bo = ob[s1 * kMaxOut];
-            return w;
-        };
-        auto decode = [&](const Raw &w, float (&ax)[4]) {
-            const float b0 = (float)((w.mk[0] >> sh) & 1u), b1 = (float)((w.mk[1] >> sh) & 1u), b2 = (float)((w.mk[2] >> sh) & 1u);
-            if (grp == 0) { ax[0] = sc0 ? w.sx : b0; ax[1] = b1; ax[2] = b2; ax[3] = ones; }
-            else { ax[0] = b0; ax[1] = b1; ax[2] = sc5 ? w.sx : b2; ax[3] = w.ah; }
-        };
-        Raw cur = load(0), nxt = load(1);
-        float ax[4];
-        decode(cur, ax);
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) {
-            Raw nn = nxt;
-            if (kk + 2 < 16) nn = load(kk + 2);
-            float axn[4];
-            decode(nxt, axn);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < 3; ++u) A.acc[u] = mfma16(ax[u], cur.bdh, A.acc[u]);
-            A.acc[3] = mfma16(ax[3], grp == 0 ? cur.bdh : cur.bo, A.acc[3]);      // group 0: ones column; group 1: H x dout
-            __builtin_amdgcn_sched_barrier(0);
-            cur = nxt;
-            nxt = nn;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ax[u] = axn[u];
-        }
-    }
+    grad_products_split8(L, qn_lds + kTile, grp, strip, r, gq, FO, A);
     if (more) __syncthreads();                        // the next tile overwrites Ps / Hs / dHs / douts / qn
 }
 
-template <int SPLIT, bool GLDS = false>
+template <bool GLDS>
 __global__ void __launch_bounds__(512) k_dqn_grad_packed8(Grad2Args ga)
 {
     UAV_HOT_PRIO();
@@ -1119,9 +996,9 @@ __global__ void __launch_bounds__(512) k_dqn_grad_packed8(Grad2Args ga)
     L_STAMP(0);
     const int step = (int)gridDim.x;
     int tile = (int)blockIdx.x;
-    grad_tile_packed8<true, SPLIT, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
+    grad_tile_packed8<true, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
     for (tile += step; tile < ga.n_tiles; tile += step)
-        grad_tile_packed8<false, SPLIT, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
+        grad_tile_packed8<false, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
     L_STAMP(5);
     // ---- the partial-gradient row of this workgroup: dW1 | db1 | dW2 | db2 | loss sum | valid count
     float *out = g.partials + (size_t)blockIdx.x * ga.stride;
@@ -1130,61 +1007,26 @@ __global__ void __launch_bounds__(512) k_dqn_grad_packed8(Grad2Args ga)
     // (round 5, measured: non-temporal stores of the row lengthen this kernel by 0.8 us and shorten the next by as much -- the 6.8 MB
     // of partial rows cross the memory system once either way)
 #define UAV_ROW_ST4(ptr, val) (*reinterpret_cast<floatx4 *>(ptr) = (val))
-    if (SPLIT == 2) {
-        // (grad_products_split8b's register layout) group 1: acc[u] = tile u of the flag columns (exact zeros at the scalar columns, which
-        // group 0 stores from its gathered tile: columns 0..10 and 86..89 are left out here); group 0: acc[0] = the gathered tile
-        // (entries 0..10 = columns 0..10, 11..14 = 86..89, 15 = db1), acc[1] = dW2^T; columns 96..99 are constant zero
-        if (grp == 1) {
-            float *t0 = out + j * kW + 4 * gq;
-            if (gq == 3) UAV_ROW_ST4(t0, A.acc[0]);                      // columns 12..15
-            else if (gq == 2) t0[3] = A.acc[0][3];                       // column 11
+    // (grad_products_split8's register layout) group 1: acc[u] = tile u of the flag columns (exact zeros at the scalar columns, which
+    // group 0 stores from its gathered tile: columns 0..10 and 86..89 are left out here); group 0: acc[0] = the gathered tile
+    // (entries 0..10 = columns 0..10, 11..14 = 86..89, 15 = db1), acc[1] = dW2^T; columns 96..99 are constant zero
+    if (grp == 1) {
+        float *t0 = out + j * kW + 4 * gq;
+        if (gq == 3) UAV_ROW_ST4(t0, A.acc[0]);                      // columns 12..15
+        else if (gq == 2) t0[3] = A.acc[0][3];                       // column 11
 #pragma unroll
-            for (int u = 1; u < 5; ++u) UAV_ROW_ST4(out + j * kW + 16 * u + 4 * gq, A.acc[u]);
-            float *t5 = out + j * kW + 80 + 4 * gq;
-            if (gq == 0 || gq == 3) UAV_ROW_ST4(t5, A.acc[5]);
-            else if (gq == 1) { t5[0] = A.acc[5][0]; t5[1] = A.acc[5][1]; }
-            else { t5[2] = A.acc[5][2]; t5[3] = A.acc[5][3]; }
-        } else {
-            const floatx4 sc = A.acc[0];
-            if (gq < 2) UAV_ROW_ST4(out + j * kW + 4 * gq, sc);                                            // columns 0..7
-            else if (gq == 2) { out[j * kW + 8] = sc[0]; out[j * kW + 9] = sc[1]; out[j * kW + 10] = sc[2]; out[j * kW + 86] = sc[3]; }
-            else { out[j * kW + 87] = sc[0]; out[j * kW + 88] = sc[1]; out[j * kW + 89] = sc[2]; out[kHid * kW + j] = sc[3]; }
-            if (gq == 0) UAV_ROW_ST4(out + j * kW + 96, (floatx4{0.0f, 0.0f, 0.0f, 0.0f}));
-            if (r < n2) UAV_ROW_ST4(out + oW2 + r * kHid + 16 * strip + 4 * gq, A.acc[1]);                  // dW2^T
-        }
-    } else if (SPLIT) {
-        // (grad_products_split8's register layout) group 0: tiles 0, 2, 4 + the gathered tile, whose entries 0..10 are columns
-        // 0..10 of tile 0 -- held by the same lanes, and exact zeros in the f16 result --, 11..14 columns 86..89 and 15 db1;
-        // group 1: tiles 1, 3, 5 without columns 86..89, and dW2^T.  Columns 96..99 are constant zero in every row.
-        if (grp == 0) {
-            floatx4 t0 = A.acc[0];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) t0[k] += (4 * gq + k <= 10) ? A.acc[3][k] : 0.0f;
-            UAV_ROW_ST4(out + j * kW + 4 * gq, t0);
-            UAV_ROW_ST4(out + j * kW + 32 + 4 * gq, A.acc[1]);
-            UAV_ROW_ST4(out + j * kW + 64 + 4 * gq, A.acc[2]);
-            if (gq == 2) out[j * kW + 86] = A.acc[3][3];
-            if (gq == 3) { out[j * kW + 87] = A.acc[3][0]; out[j * kW + 88] = A.acc[3][1]; out[j * kW + 89] = A.acc[3][2];
-                           out[kHid * kW + j] = A.acc[3][3]; }
-            if (gq == 0) *reinterpret_cast<floatx4 *>(out + j * kW + 96) = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-        } else {
-            UAV_ROW_ST4(out + j * kW + 16 + 4 * gq, A.acc[0]);
-            UAV_ROW_ST4(out + j * kW + 48 + 4 * gq, A.acc[1]);
-            float *t5 = out + j * kW + 80 + 4 * gq;                      // tile 5 = columns 80..95; 86..89 belong to group 0
-            if (gq == 0 || gq == 3) *reinterpret_cast<floatx4 *>(t5) = A.acc[2];
-            else if (gq == 1) { t5[0] = A.acc[2][0]; t5[1] = A.acc[2][1]; }
-            else { t5[2] = A.acc[2][2]; t5[3] = A.acc[2][3]; }
-            if (r < n2) *reinterpret_cast<floatx4 *>(out + oW2 + r * kHid + 16 * strip + 4 * gq) = A.acc[3];      // dW2^T
-        }
-    } else if (grp == 0) {
-#pragma unroll
-        for (int u = 0; u < 3; ++u) *reinterpret_cast<floatx4 *>(out + j * kW + 32 * u + 4 * gq) = A.acc[u];     // tiles 0, 2, 4
-        if (gq == 0) *reinterpret_cast<floatx4 *>(out + j * kW + 96) = A.acc[3];                                // tile 6: columns 96..99
-        else if (gq == 1) out[kHid * kW + j] = A.acc[3][0];                                                      // column 100 -> db1[j]
+        for (int u = 1; u < 5; ++u) UAV_ROW_ST4(out + j * kW + 16 * u + 4 * gq, A.acc[u]);
+        float *t5 = out + j * kW + 80 + 4 * gq;
+        if (gq == 0 || gq == 3) UAV_ROW_ST4(t5, A.acc[5]);
+        else if (gq == 1) { t5[0] = A.acc[5][0]; t5[1] = A.acc[5][1]; }
+        else { t5[2] = A.acc[5][2]; t5[3] = A.acc[5][3]; }
     } else {
-#pragma unroll
-        for (int u = 0; u < 3; ++u) *reinterpret_cast<floatx4 *>(out + j * kW + 16 + 32 * u + 4 * gq) = A.acc[u]; // tiles 1, 3, 5
-        if (r < n2) *reinterpret_cast<floatx4 *>(out + oW2 + r * kHid + 16 * strip + 4 * gq) = A.acc[3];          // dW2^T
+        const floatx4 sc = A.acc[0];
+        if (gq < 2) UAV_ROW_ST4(out + j * kW + 4 * gq, sc);                                            // columns 0..7
+        else if (gq == 2) { out[j * kW + 8] = sc[0]; out[j * kW + 9] = sc[1]; out[j * kW + 10] = sc[2]; out[j * kW + 86] = sc[3]; }
+        else { out[j * kW + 87] = sc[0]; out[j * kW + 88] = sc[1]; out[j * kW + 89] = sc[2]; out[kHid * kW + j] = sc[3]; }
+        if (gq == 0) UAV_ROW_ST4(out + j * kW + 96, (floatx4{0.0f, 0.0f, 0.0f, 0.0f}));
+        if (r < n2) UAV_ROW_ST4(out + oW2 + r * kHid + 16 * strip + 4 * gq, A.acc[1]);                  // dW2^T
     }
     if (grp == 0 && lane == 0) {
 #pragma unroll
@@ -1339,190 +1181,6 @@ __device__ __forceinline__ void fwd_strip_h(const _Float16 *W, const _Float16 *s
         for (int t = 0; t < 4; ++t)
             acc[t] = mfma16h(*reinterpret_cast<const half8 *>(wp + t * 16 * kLdH + 32 * kk), b, acc[t]);
     }
-}
-
-struct GradLdsH {
-    _Float16 *W1l, *W1t, *Xs, *Xn, *XsT, *HT, *dHT, *doutT;     // HT / dHT alias the Xn tile (dead after the forward passes)
-    float *W2l, *W2t, *b2l, *b2t, *red;
-    uint32_t *stage;
-};
-
-// what a tile needs from HBM: its 2 x 16 observation rows per wavefront and each lane's transition scalars
-struct TileLoads {
-    floatx4 vXs[kXIters], vXn[kXIters];
-    int p_act, smp;
-    float p_rew, p_done, p_valid, p_w;
-};
-
-template <int KIND>
-__device__ __forceinline__ void tile_issue(const GradArgs &g, int tile, TileLoads &T)
-{
-    const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6, r = lane & 15;
-    const int smp = tile * kTile + wv * 16 + r;
-    int f, agent;
-    if (g.explicit_idx) {
-        f = g.explicit_idx[2 * smp];
-        agent = g.explicit_idx[2 * smp + 1];
-    } else {
-        replay_slot_to_frame(g.perm, replay_perm_apply(g.perm, (uint32_t)smp), g.head, g.ring.frames, f, agent);
-    }
-    int fn = f + 1;
-    if (fn >= g.ring.frames) fn = 0;
-    const uint32_t row_s = (uint32_t)f * (uint32_t)g.ring.n_agents + (uint32_t)agent;
-    const uint32_t row_n = (uint32_t)fn * (uint32_t)g.ring.n_agents + (uint32_t)agent;
-    xh_issue<KIND>(T.vXs, g.ring.obs, row_s);
-    {
-        uint32_t raw_done, raw_valid;
-        load_transition(g.ring, row_s, T.p_act, T.p_rew, raw_done, raw_valid);
-        T.p_done = (float)raw_done;
-        T.p_valid = (float)raw_valid;
-    }
-    T.p_w = g.is_w ? g.is_w[smp] : 1.0f;
-    T.smp = smp;
-    xh_issue<KIND>(T.vXn, g.ring.obs, row_n);
-}
-
-// One tile.  T holds this tile's loads (issued by the caller / the previous tile); when `more`, the NEXT tile's loads are
-// issued into T as soon as this tile's rows have been committed to LDS, so that their HBM round trip runs under the
-// TD / backward / gradient-product phases (a workgroup of BASELINE configs[2] walks four tiles).
-template <int KIND, int NMAX, bool FIRST>
-__device__ __forceinline__ void grad_tile_h(const GradArgs &g, const GradLdsH &L, int tile, int next_tile, bool more,
-                                            TileLoads &T, GradAcc<NMAX> &A)
-{
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 15, gq = lane >> 4;
-    const int n2 = g.n_actions + (g.dueling ? 1 : 0);
-    _Float16 *xs_strip = L.Xs + wv * 16 * kLdH, *xn_strip = L.Xn + wv * 16 * kLdH;
-    floatx4 vWl[kStageIters], vWt[kStageIters];
-    float pb1 = 0.0f, pb1t = 0.0f, pw[4] = {0, 0, 0, 0}, pt[4] = {0, 0, 0, 0}, pb2 = 0.0f, pb2t = 0.0f;
-    if (FIRST) {
-        w_issue(vWl, g.local);
-        const NetDev nl = net_view(g.local, n2), nt = net_view(g.target, n2);
-        const int kb = tid < kHid ? tid : kHid - 1;
-        pb1 = nl.b1[kb]; pb1t = nt.b1[kb];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int idx = tid + 256 * k < n2 * kHid ? tid + 256 * k : 0;
-            pw[k] = nl.W2[idx]; pt[k] = nt.W2[idx];
-        }
-        const int kq = tid < n2 ? tid : 0;
-        pb2 = nl.b2[kq]; pb2t = nt.b2[kq];
-        tile_issue<KIND>(g, tile, T);
-        w_issue(vWt, g.target);
-    }
-    const int p_act = T.p_act, smp = T.smp;
-    const float p_rew = T.p_rew, p_done = T.p_done, p_valid = T.p_valid, p_w = T.p_w;
-
-    uint32_t *stage = L.stage + wv * kStageW;
-    if (FIRST) wh_commit(L.W1l, vWl, pb1);
-    xh_commit<KIND>(xs_strip, T.vXs, stage, L.XsT + wv * 16);
-    wave_lds_sync();
-    if (FIRST) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (tid + 256 * k < n2 * kHid) { L.W2l[tid + 256 * k] = pw[k]; L.W2t[tid + 256 * k] = pt[k]; }
-        if (tid < n2) { L.b2l[tid] = pb2; L.b2t[tid] = pb2t; }
-        for (int k = tid; k < 16 * kLdT / 2; k += 256) reinterpret_cast<uint32_t *>(L.doutT)[k] = 0u;     // rows >= n2 stay zero
-        __syncthreads();
-    }
-    L_STAMP(1);
-    floatx4 hl[4];
-    fwd_strip_h(L.W1l, xs_strip, hl);
-    W2Frag<NMAX> Fl;
-    w2_load<NMAX, 3>(Fl, L.W2l, L.b2l, n2);
-    float ql[NMAX];
-    q_strip<NMAX, 3>(hl, Fl, n2, g.n_actions, g.dueling, ql);
-    xh_commit<KIND>(xn_strip, T.vXn, stage, nullptr);
-    if (FIRST) {
-        wh_commit(L.W1t, vWt, pb1t);
-        __syncthreads();
-    }
-    wave_lds_sync();
-    if (more) tile_issue<KIND>(g, next_tile, T);      // the next tile's HBM round trip starts here
-    L_STAMP(2);
-    int best = 0;
-    floatx4 ht[4];
-    if (g.kind == 1) {                        // double DQN: a* = argmax_a Q_local(s', a)   (DDQN_Trainer.py:94)
-        fwd_strip_h(L.W1l, xn_strip, ht);
-        float qn_l[NMAX];
-        q_strip<NMAX, 3>(ht, Fl, n2, g.n_actions, g.dueling, qn_l);
-        float bq = qn_l[0];
-#pragma unroll
-        for (int a = 1; a < NMAX; ++a)
-            if (a < g.n_actions && qn_l[a] > bq) { bq = qn_l[a]; best = a; }
-    }
-    fwd_strip_h(L.W1t, xn_strip, ht);
-    float qt[NMAX];
-    {
-        W2Frag<NMAX> Ft;
-        w2_load<NMAX, 3>(Ft, L.W2t, L.b2t, n2);
-        q_strip<NMAX, 3>(ht, Ft, n2, g.n_actions, g.dueling, qt);
-    }
-    L_STAMP(3);
-    __syncthreads();                                  // every wave is done with its s' rows: HT / dHT overwrite that tile
-    const int s = wv * 16 + r;
-    td_backward<NMAX, true>(g, L.W2l, hl, Fl, ql, pick_qn<NMAX>(g, qt, best), p_act, p_rew, p_done, p_valid, p_w, smp, A,
-                            reinterpret_cast<float *>(L.HT + s), reinterpret_cast<float *>(L.dHT + s),
-                            reinterpret_cast<float *>(L.doutT + s));
-    __syncthreads();
-    L_STAMP(4);
-    // ---- weight gradients, K = 64 samples = 2 MFMA steps of 32:
-    //   dW1^T[k][j] += sum_s XsT[k][s] dHT[j][s]   (7 tiles of 16 k-columns, hidden units 16 wv + r)
-    //   dW2^T[j][a] += sum_s HT[j][s] doutT[a][s]
-    {
-        const _Float16 *xa = L.XsT + r * kLdT + 8 * gq;
-        const _Float16 *db = L.dHT + (16 * wv + r) * kLdT + 8 * gq;
-        const _Float16 *ha = L.HT + (16 * wv + r) * kLdT + 8 * gq;
-        const _Float16 *ob = L.doutT + r * kLdT + 8 * gq;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const half8 bdh = *reinterpret_cast<const half8 *>(db + 32 * kk);
-#pragma unroll
-            for (int u = 0; u < 7; ++u)
-                A.acc1[u] = mfma16h(*reinterpret_cast<const half8 *>(xa + 16 * u * kLdT + 32 * kk), bdh, A.acc1[u]);
-            A.acc2 = mfma16h(*reinterpret_cast<const half8 *>(ha + 32 * kk), *reinterpret_cast<const half8 *>(ob + 32 * kk), A.acc2);
-        }
-    }
-    if (more) __syncthreads();
-}
-
-template <int KIND, int NMAX>
-__global__ void __launch_bounds__(256) k_dqn_grad_h(Grad2Args ga)
-{
-    const GradArgs &g = ga.g;
-    extern __shared__ __align__(16) float lds[];
-    GradLdsH L;
-    _Float16 *hb = reinterpret_cast<_Float16 *>(lds);
-    L.W1l = hb;                              // [64][136]
-    L.W1t = L.W1l + kTile * kLdH;
-    L.Xs = L.W1t + kTile * kLdH;
-    L.Xn = L.Xs + kTile * kLdH;              // [64][136] = 8 704 halfs; later HT [64][72] + dHT [64][72] = 9 216 halfs
-    L.HT = L.Xn;
-    L.dHT = L.HT + kTile * kLdT;
-    L.XsT = L.Xn + 2 * kTile * kLdT;         // [112][72]
-    L.doutT = L.XsT + 112 * kLdT;            // [16][72]
-    L.W2l = reinterpret_cast<float *>(L.doutT + 16 * kLdT);
-    L.W2t = L.W2l + kMaxOut * kHid;
-    L.b2l = L.W2t + kMaxOut * kHid;
-    L.b2t = L.b2l + kMaxOut;
-    L.red = L.b2t + kMaxOut;
-    L.stage = reinterpret_cast<uint32_t *>(L.red + 4 * (kMaxOut + 2));
-    // XsT rows 101..111 feed output rows nobody stores; zeroed once so that no NaN bit pattern ever enters an MFMA
-    for (int k = (int)threadIdx.x; k < 11 * kLdT / 2; k += 256) reinterpret_cast<uint32_t *>(L.XsT + 101 * kLdT)[k] = 0u;
-    GradAcc<NMAX> A;
-    A.acc2 = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int u = 0; u < 7; ++u) A.acc1[u] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int a = 0; a < NMAX + 2; ++a) A.csum[a] = 0.0f;
-    L_STAMP(0);
-    const int step = (int)gridDim.x;
-    int tile = (int)blockIdx.x;
-    TileLoads T;
-    grad_tile_h<KIND, NMAX, true>(g, L, tile, tile + step, tile + step < ga.n_tiles, T, A);
-    for (tile += step; tile < ga.n_tiles; tile += step)
-        grad_tile_h<KIND, NMAX, false>(g, L, tile, tile + step, tile + step < ga.n_tiles, T, A);
-    L_STAMP(5);
-    grad_write_partials<NMAX>(g, ga.stride, L.red, A);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1773,9 +1431,6 @@ __global__ void __launch_bounds__(512) k_dqn_grad_h8(Grad2Args ga)
 
 constexpr size_t kGradH8Lds = (size_t)(4 * kTile * kLdH + 2 * kTile * kLdT + 2 * 112 * kLdT + 16 * kLdT) * 2 +
                               (size_t)(2 * kMaxOut * kHid + 2 * kMaxOut + 4 * (kMaxOut + 2) + 2 * kTile + 8 * kStageW) * 4;
-
-constexpr size_t kGradHLds = (size_t)(3 * kTile * kLdH + 2 * kTile * kLdT + 112 * kLdT + 16 * kLdT) * 2 +
-                             (size_t)(2 * kMaxOut * kHid + 2 * kMaxOut + 4 * (kMaxOut + 2) + 4 * kStageW) * 4;
 
 template <typename ObsT, int NMAX>
 __global__ void __launch_bounds__(256) k_dqn_grad(Grad2Args ga)
@@ -2285,20 +1940,6 @@ bool net_ok(const UavDqnNet *n)
 }
 
 template <int KIND>
-static int launch_grad_h(const Grad2Args &ga, int grid, hipStream_t s)
-{
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_h<KIND, 4>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradHLds) != hipSuccess)
-            return UAVENV_EHIP;
-        attr = true;
-    }
-    hipLaunchKernelGGL((k_dqn_grad_h<KIND, 4>), dim3(grid), dim3(256), kGradHLds, s, ga);
-    return UAVENV_OK;
-}
-
-template <int KIND>
 static int launch_grad_h8(const Grad2Args &ga, int grid, hipStream_t s)
 {
     static bool attr = false;
@@ -2347,17 +1988,30 @@ static int launch_act(const ActArgs &g, int grid, hipStream_t s)
     return UAVENV_OK;
 }
 
-template <int NMAX>
-static int launch_grad_packed(const Grad2Args &ga, int grid, hipStream_t s)
+static int launch_grad_packed(const Grad2Args &ga, int grid, hipStream_t s)       // packed rows, more than 4 layer-2 outputs
 {
     static bool attr = false;
     if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed<NMAX>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed<kMaxOut - 2>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradPLds) != hipSuccess)
             return UAVENV_EHIP;
         attr = true;
     }
-    hipLaunchKernelGGL((k_dqn_grad_packed<NMAX>), dim3(grid), dim3(256), kGradPLds, s, ga);
+    hipLaunchKernelGGL((k_dqn_grad_packed<kMaxOut - 2>), dim3(grid), dim3(256), kGradPLds, s, ga);
+    return UAVENV_OK;
+}
+
+template <bool GLDS>
+static int launch_grad_packed8(const Grad2Args &ga, int grid, hipStream_t s)
+{
+    static bool attr = false;
+    if (!attr) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed8<GLDS>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess)
+            return UAVENV_EHIP;
+        attr = true;
+    }
+    hipLaunchKernelGGL((k_dqn_grad_packed8<GLDS>), dim3(grid), dim3(512), kGradP8Lds, s, ga);
     return UAVENV_OK;
 }
 
@@ -2461,47 +2115,18 @@ int uavenv_dqn_grad_img(const UavReplayRing *ring, int32_t head, int32_t filled,
     int rc;
     if (net->mfma_dtype == UAVENV_MFMA_F16) {         // f16 operands, f32 accumulate: f16 / packed rings, <= 4 layer-2 outputs
         if (!small || ring->obs_dtype == UAVENV_OBS_F32) return UAVENV_EINVAL;
-        static const bool four_waves_h = getenv("UAVENV_GRAD_4WAVES") != nullptr;    // A/B knob
-        if (four_waves_h)
-            rc = ring->obs_dtype == UAVENV_OBS_PACKED ? launch_grad_h<OBS_KIND_PACKED>(ga, grid, s) : launch_grad_h<OBS_KIND_F16>(ga, grid, s);
-        else
-            rc = ring->obs_dtype == UAVENV_OBS_PACKED ? launch_grad_h8<OBS_KIND_PACKED>(ga, grid, s) : launch_grad_h8<OBS_KIND_F16>(ga, grid, s);
+        rc = ring->obs_dtype == UAVENV_OBS_PACKED ? launch_grad_h8<OBS_KIND_PACKED>(ga, grid, s) : launch_grad_h8<OBS_KIND_F16>(ga, grid, s);
     } else if (ring->obs_dtype == UAVENV_OBS_F32)
         rc = small ? launch_grad<float, 4>(ga, grid, s) : launch_grad<float, kMaxOut - 2>(ga, grid, s);
-    else if (ring->obs_dtype == UAVENV_OBS_PACKED) {
-        static const bool four_waves = getenv("UAVENV_GRAD_4WAVES") != nullptr;      // A/B knob
-        if (small && !four_waves) {
-            // UAVENV_DW1_F32=1: the round-4 form of the weight-gradient products (all on the f32 matrix pipe) -- A/B knob
-            static const bool dw1_f32 = getenv("UAVENV_DW1_F32") != nullptr;
-            static bool attr8 = false;
-            // form B of the split products (group 1 all six flag tiles, their operands built while group 0 is in td_backward) is the
-            // default: 11.48 -> 10.75 us per launch, 28.76 -> 28.2 us per configs[1] pass; UAVENV_DW1_SPLITA=1 selects form A
-            static const bool dw1_b = getenv("UAVENV_DW1_SPLITA") == nullptr;
-            // (with a layer-1 image: form B stages both images by LDS-DMA; UAVENV_STAGE_VGPR=1 keeps the register-staged form -- A/B knob)
-            static const bool stage_vgpr = getenv("UAVENV_STAGE_VGPR") && atoi(getenv("UAVENV_STAGE_VGPR")) != 0;
-            if (!attr8) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed8<1>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed8<2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed8<2, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed8<0>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess)
-                    return UAVENV_EHIP;
-                attr8 = true;
-            }
-            if (dw1_f32) hipLaunchKernelGGL(k_dqn_grad_packed8<0>, dim3(grid), dim3(512), kGradP8Lds, s, ga);
-            else if (dw1_b && g.img && !stage_vgpr) hipLaunchKernelGGL((k_dqn_grad_packed8<2, true>), dim3(grid), dim3(512), kGradP8Lds, s, ga);
-            else if (dw1_b) hipLaunchKernelGGL(k_dqn_grad_packed8<2>, dim3(grid), dim3(512), kGradP8Lds, s, ga);
-            else hipLaunchKernelGGL(k_dqn_grad_packed8<1>, dim3(grid), dim3(512), kGradP8Lds, s, ga);
-            rc = UAVENV_OK;
-        } else {
-            rc = small ? launch_grad_packed<4>(ga, grid, s) : launch_grad_packed<kMaxOut - 2>(ga, grid, s);
-        }
-    }
-    else
+    else if (ring->obs_dtype != UAVENV_OBS_PACKED)
         rc = small ? launch_grad<__half, 4>(ga, grid, s) : launch_grad<__half, kMaxOut - 2>(ga, grid, s);
+    else if (small) {
+        // with a layer-1 image both images are staged by LDS-DMA; UAVENV_STAGE_VGPR=1 keeps the register-staged form, the reference
+        // that the DMA staging is held to bit for bit
+        static const bool stage_vgpr = getenv("UAVENV_STAGE_VGPR") && atoi(getenv("UAVENV_STAGE_VGPR")) != 0;
+        rc = g.img && !stage_vgpr ? launch_grad_packed8<true>(ga, grid, s) : launch_grad_packed8<false>(ga, grid, s);
+    } else
+        rc = launch_grad_packed(ga, grid, s);
     if (rc != UAVENV_OK) return rc;
     return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
 }

@@ -56,21 +56,8 @@ constexpr int kStrideA = UAVENV_SAC_ACTOR_STRIDE;  // kPa + [actor loss sum, sum
 constexpr int kStrideC = UAVENV_SAC_CRITIC_STRIDE; // 2 kPc + [loss 1 sum, loss 2 sum, 0, 0]
 static_assert(kStrideA == kPa + 4 && kStrideC == 2 * kPc + 4, "partial-row strides");
 constexpr int kTMax = 8;                           // tiles per workgroup
-// The 64 -> 64 layer's forward as a three-term f16 product in k_sac_td and the critic phase (layer2_fwd_h): BUILT, MEASURED, OFF.
-// configs[3], one MI355X: 0.4980 ms per pass with the layer on the f32 matrix pipe, 0.5108 ms with the f16 form (all 18 SAC tests
-// green either way) -- 24 f16 MFMAs replace 64 f32 ones, but splitting the lane's 16 activations (max, scale, two conversions each)
-// and the second accumulator's fix-up are ~150 VALU instructions of the SAME wavefront, which do not overlap its MFMAs: with one
-// wavefront per SIMD the phase is bound by its instruction stream, not by the matrix pipe.  -DUAVENV_SAC_W2_HALF builds it.
-#ifdef UAVENV_SAC_W2_HALF
-constexpr bool kSacW2Half = true;
-#else
-constexpr bool kSacW2Half = false;
-#endif
-#ifdef UAVENV_SAC_DW1_F32
-constexpr bool kSacSplitDw1 = false;               // A/B build: the round-4 form of dW1 (all on the f32 matrix pipe)
-#else
-constexpr bool kSacSplitDw1 = true;                // dW1 in the split form (wgrad_x_split)
-#endif
+// Measured and retired: the 64 -> 64 layer's forward as a three-term f16 product, 0.5108 against 0.4980 ms per configs[3] pass (its
+// VALU split work does not overlap the wavefront's own MFMAs); dW1 all on the f32 pipe, 0.5225 against 0.4998.  Last tree with both: 55f65ee.
 // Tiles per workgroup of a launch that covers n_slots trainers of n_tiles tiles each: as many as it takes to bring the launch
 // down to one workgroup per CU (the staged nets -- ~26 k cycles per workgroup -- and the partial row are paid per workgroup,
 // not per tile), at most kTMax.  BASELINE configs[3]: 4 slots x 512 tiles -> 8 tiles per workgroup, 256 workgroups; one
@@ -140,7 +127,7 @@ constexpr int kPsLd = 28;                          // dwords per sample of the p
 // LDS maps (floats).  Critic phase, stage I: actor fc1 | target 1 | target 2; stage II: critic | X | H1 H2 dH1 dH2 | dq | red;
 // the td targets of the workgroup's tiles live behind both.  Actor phase: actor fc1 | critic 1 | critic 2 | Ps | H dH | dq | red.
 constexpr int kTdSetF_ = 2 * kHid * 88 * 2 / 4 + kHid * 20 + kHid * kLh + kHid;       // = kTdSetF (defined with the split layer 1 below)
-constexpr int kCritStage2F = kTdSetF_ + kTileF + 4 * kTile * kLh + kTile * 4 + 64;   // (the critic phase keeps an f32 X tile)
+constexpr int kCritStage2F = kTdSetF_ + kTileF + 4 * kTile * kLh + kTile * 4 + 64;   // (X: an f32 tile's worth, of which the packed rows use kTile * kPsLd)
 constexpr int kCritTdOff = kCritStage2F > kTileF + 2 * kWSetF ? kCritStage2F : kTileF + 2 * kWSetF;
 constexpr size_t kSacCriticLds = (size_t)(kCritTdOff + kTMax * kTile * 3) * 4;      // td targets [.][2] + critic 1's Q[0] per sample
 constexpr size_t kSacActorLds = (size_t)(kTileF + 2 * kWSetF + kTile * kPsLd + 2 * kTile * kLh + kTile * 4 + 64) * 4;   // (the split forms: same sizes)
@@ -293,99 +280,6 @@ __device__ __forceinline__ void layer2_bwd(const WSet &S, const floatx4 (&dh2)[4
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Round 5: the 64 -> 64 layer's FORWARD off the f32 matrix pipe.  Neither operand is exact in f16 here, so
-// both are split: fc2 as hi + mid 2^-11 (staged once per workgroup, W2Half), the lane's post-ReLU activations as hi + mid 2^-11 of
-// h 2^S, S from the SAMPLE's largest activation (an MFMA's B column is one sample: a per-sample scale factors out of its output
-// column exactly).  Three v_mfma_f32_16x16x32_f16 per (16 outputs, 32 inputs): hi x hi into one accumulator, mid x hi and hi x mid
-// into a second one worth 2^-11 (mid x mid, 2^-22 relative, is dropped): 24 MFMAs of 16 cycles instead of 64 of 32, sums in f32,
-// ~2^-21 relative per product.  The K index of a lane group keeps the chaining trick of layer2_fwd: element i of lane group g in K
-// block kb is hidden unit 16 (2 kb + (i >> 2)) + 4 g + (i & 3) -- the registers this lane holds.  The staged image is stored in
-// MFMA order, [t2][kb][lane][8 halves]: every A operand is one conflict-free 16-byte read.  Forward only: the backward (W2^T) would
-// need a transposed image the LDS maps have no room for.
-// ---------------------------------------------------------------------------------------------------------------------
-constexpr int kW2hTerm = 4 * 2 * 64 * 8;                   // halves per term: 8 KB; hi + mid = 16 KB (4 096 floats)
-struct W2Half {
-    _Float16 *hi, *mid;
-};
-__device__ __forceinline__ W2Half w2half_at(float *p)
-{
-    W2Half I;
-    I.hi = reinterpret_cast<_Float16 *>(p);
-    I.mid = I.hi + kW2hTerm;
-    return I;
-}
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-// fc2 from the registers of critic_issue (thread tid, piece it: row (it 256 + tid) >> 4, input units 4 q .. 4 q + 3); 256 threads
-__device__ __forceinline__ void layer2_commit_h(const W2Half &I, const CritRegs &C)
-{
-    const int tid = (int)threadIdx.x & 255;
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int c = it * 256 + tid, row = c >> 4, q = c & 15;
-        const int t2 = row >> 4, r = row & 15, t = q >> 2, g = q & 3, kb = t >> 1;
-        const int idx = (((t2 * 2 + kb) * 64 + 16 * g + r) * 8) + 4 * (t & 1);
-        half4v h, l;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float w = C.w2[it][k];
-            h[k] = (_Float16)w;
-            l[k] = (_Float16)((w - (float)h[k]) * 2048.0f);
-        }
-        *reinterpret_cast<half4v *>(I.hi + idx) = h;
-        *reinterpret_cast<half4v *>(I.mid + idx) = l;
-    }
-}
-// max over the four lane groups of a sample (lanes l, l ^ 16, l ^ 32, l ^ 48), in all of them (group_sum4 with max)
-__device__ __forceinline__ float group_max4(float v)
-{
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    a = fmaxf(a, b);
-    b = a;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ void layer2_fwd_h(const W2Half &I, const float *b2s, const floatx4 (&h1)[4], floatx4 (&acc2)[4])
-{
-    const int lane = (int)threadIdx.x & 63, g = lane >> 4;
-    float m = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) m = fmaxf(m, h1[t][k]);                  // (post-ReLU: >= 0)
-    float up, down;
-    split_scale(group_max4(m), up, down);
-    floatx4 cm[4], cc[4];
-#pragma unroll
-    for (int t2 = 0; t2 < 4; ++t2) { cm[t2] = floatx4{0.0f, 0.0f, 0.0f, 0.0f}; cc[t2] = floatx4{0.0f, 0.0f, 0.0f, 0.0f}; }
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-        half8 ah[4], am[4];
-#pragma unroll
-        for (int t2 = 0; t2 < 4; ++t2) {
-            ah[t2] = *reinterpret_cast<const half8 *>(I.hi + ((t2 * 2 + kb) * 64 + lane) * 8);
-            am[t2] = *reinterpret_cast<const half8 *>(I.mid + ((t2 * 2 + kb) * 64 + lane) * 8);
-        }
-        const float w[8] = {h1[2 * kb][0], h1[2 * kb][1], h1[2 * kb][2], h1[2 * kb][3],
-                            h1[2 * kb + 1][0], h1[2 * kb + 1][1], h1[2 * kb + 1][2], h1[2 * kb + 1][3]};
-        half8 bh, bm;
-        split_half8(w, up, bh, bm);
-#pragma unroll
-        for (int t2 = 0; t2 < 4; ++t2) cm[t2] = mfma16h(ah[t2], bh, cm[t2]);
-#pragma unroll
-        for (int t2 = 0; t2 < 4; ++t2) cc[t2] = mfma16h(am[t2], bh, cc[t2]);
-#pragma unroll
-        for (int t2 = 0; t2 < 4; ++t2) cc[t2] = mfma16h(ah[t2], bm, cc[t2]);
-    }
-#pragma unroll
-    for (int t2 = 0; t2 < 4; ++t2) {
-        const floatx4 b = *reinterpret_cast<const floatx4 *>(b2s + 16 * t2 + 4 * g);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc2[t2][k] = fmaf(fmaf(cc[t2][k], 1.0f / 2048.0f, cm[t2][k]), down, b[k]);
-    }
-}
-
 // Q(s, a) of a staged critic for this lane's sample; acc1 / acc2 keep the pre-activations
 __device__ __forceinline__ void critic_fwd(const WSet &S, const PRow &R, float a0, float a1, const W2Frag<2> &Fo,
                                            floatx4 (&acc1)[4], floatx4 (&acc2)[4], float (&q)[2])
@@ -467,89 +361,8 @@ __device__ __forceinline__ void h_strip_store(float *Hs, const floatx4 (&h)[4])
     for (int t = 0; t < 4; ++t) *reinterpret_cast<floatx4 *>(Hs + (16 * wv + r) * kLh + 16 * t + 4 * g) = h[t];
 }
 
-// Weight-gradient products over the tile's 64 samples (K = samples): acc[reg] += sum_s A[s][16 wave + 4 g + reg] B[s][n].
-// MFMA step k, lane group g: sample (k & 3) + 16 (k >> 2) + 4 g -- rows 4 apart are 16 (48 for the packed rows) banks apart.
-// The operands of four steps are requested together, then their MFMAs run (one ds_read -> wait -> MFMA per step left
-// the matrix pipe idle two thirds of the time: 109 cycles per MFMA, measured).
-//
-// dW1: B = the f32 row the packed-row tile stands for (tile columns 0..111; 100 = 1, 101 / 102 = the action when EXT).
-// The lane's column per u is fixed, so where its value sits in a row (a scalar dword, or a bit of a flag word) is
-// worked out once, outside the sample loop.
-template <bool EXT>
-__device__ __forceinline__ void wgrad_x(const float *As, const uint32_t *Ps, floatx4 (&acc)[7])
-{
-    const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-    int dw[7], sh[7];
-    bool sc[7];
-#pragma unroll
-    for (int u = 0; u < 7; ++u) {
-        const int c = 16 * u + r;
-        sh[u] = 0;
-        sc[u] = true;
-        if (c < 11) dw[u] = 4 + c;
-        else if (c >= 86 && c < 90) dw[u] = 15 + (c - 86);
-        else if (c == kW) dw[u] = 20;
-        else if (EXT && (c == kW + 1 || c == kW + 2)) dw[u] = 20 + (c - kW);
-        else if (c >= 95) dw[u] = 3;                                // constant-zero columns (dword 3 of a row is 0)
-        else { dw[u] = c >> 5; sh[u] = c & 31; sc[u] = false; }
-    }
-    const float *ap = As + 4 * g * kLh + 16 * wv + r;
-    const uint32_t *pp = Ps + 4 * g * kPsLd;
-#pragma unroll
-    for (int kc = 0; kc < 4; ++kc) {
-        float a[4];
-        uint32_t w[4][7];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int s = kk + 16 * kc;
-            a[kk] = ap[s * kLh];
-#pragma unroll
-            for (int u = 0; u < 7; ++u) w[kk][u] = pp[s * kPsLd + dw[u]];
-        }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int u = 0; u < 7; ++u) {
-                const float b = sc[u] ? __uint_as_float(w[kk][u]) : (float)((w[kk][u] >> sh[u]) & 1u);
-                acc[u] = mfma16(a[kk], b, acc[u]);
-            }
-    }
-}
-// this strip's 16 rows of an f32 X tile [64][kLd] (columns 0..103; 100 = 1, 101 / 102 = the action) from the lanes' packed rows
-__device__ __forceinline__ void x_strip_store(float *Xs, const PRow &R, float a0, float a1)
-{
-    const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-    const uint32_t slice = prow_slice(R, g);
-    float *dst = Xs + (16 * wv + r) * kLd + 26 * g;
-#pragma unroll
-    for (int i = 0; i < 13; ++i) *reinterpret_cast<float2 *>(dst + 2 * i) = prow_pair<true>(R, slice, g == 0, g == 3, i, a0, a1);
-}
-// dW1 with B read from that tile: no decode between the MFMAs (the VALU of a wavefront does not overlap its own MFMAs: the
-// packed-row decode made this product 7.5 k cycles per tile against 3.6 k of MFMA issue; the actor phase has no LDS for an
-// f32 tile next to its three resident nets and keeps wgrad_x)
-__device__ __forceinline__ void wgrad_xf(const float *As, const float *Xs, floatx4 (&acc)[7])
-{
-    const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-    const float *ap = As + 4 * g * kLh + 16 * wv + r;
-    const float *bp = Xs + 4 * g * kLd + r;
-#pragma unroll
-    for (int kc = 0; kc < 4; ++kc) {
-        float a[4], b[4][7];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int s = kk + 16 * kc;
-            a[kk] = ap[s * kLh];
-#pragma unroll
-            for (int u = 0; u < 7; ++u) b[kk][u] = bp[s * kLd + 16 * u];
-        }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int u = 0; u < 7; ++u) acc[u] = mfma16(a[kk], b[kk][u], acc[u]);
-    }
-}
 // ---------------------------------------------------------------------------------------------------------------------
-// Round 5: dW1 in the SPLIT form (as learner.hip: grad_products_split8).  80 of the 100 observation columns are 0 / 1 flags -- exact
+// dW1 in the SPLIT form (as learner.hip: grad_products_split8).  80 of the 100 observation columns are 0 / 1 flags -- exact
 // in f16 -- so their part of dW1[j][c] = sum_s dH1[s][j] X[s][c] runs on v_mfma_f32_16x16x32_f16 with dH1 as two f16 terms (hi +
 // mid 2^-11 of dH1 2^S; 2^S from the tile's largest |dH1|: no overflow, 22-23 significant bits relative to it; every product
 // exact, f32 sums); the 15 scalar columns and the ones column (-> db1) form one gathered 16-entry tile on v_mfma_f32_16x16x4_f32
@@ -645,7 +458,7 @@ __device__ __forceinline__ void wgrad_x_split(const float *dHs, const uint32_t *
         W.act[1] += s1a;
     }
 }
-// ... -> the partial row (the layout of store_dw1: input column c < 100 at [j][c], b1 at ob1 + j, the action columns at [j][100], [j][101])
+// ... -> the partial row (input column c < 100 at [j][c], b1 at ob1 + j, the action columns at [j][100], [j][101])
 template <bool EXT>
 __device__ __forceinline__ void store_dw1_split(float *out, int in_dim, int ob1, Dw1Split &W)
 {
@@ -672,6 +485,11 @@ __device__ __forceinline__ void store_dw1_split(float *out, int in_dim, int ob1,
     }
 }
 
+// The other weight-gradient products over the tile's 64 samples (K = samples): acc[reg] += sum_s A[s][16 wave + 4 g + reg] B[s][n].
+// MFMA step k, lane group g: sample (k & 3) + 16 (k >> 2) + 4 g -- rows 4 apart are 16 banks apart.
+// The operands of four steps are requested together, then their MFMAs run (one ds_read -> wait -> MFMA per step left
+// the matrix pipe idle two thirds of the time: 109 cycles per MFMA, measured).
+//
 // the critic's other products in one sweep: dW2 = dH2^T H1 (4 tiles), dWout^T = H2^T dq, db2 = column sums of dH2
 __device__ __forceinline__ void wgrad_critic_rest(const float *dH2s, const float *H1s, const float *H2s, const float *dqs,
                                                   floatx4 (&aw2)[4], floatx4 &awo, floatx4 &ab2)
@@ -715,23 +533,6 @@ __device__ __forceinline__ void wgrad_small(const float *As, const float *small,
     }
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc = mfma16(a[k], b[k], acc);
-}
-
-// fc1 gradient tiles -> the partial row: tile column c < 100 -> input column c, 100 -> b1, 101 / 102 -> the action columns
-__device__ __forceinline__ void store_dw1(float *out, int in_dim, int ob1, const floatx4 (&acc)[7])
-{
-    const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-#pragma unroll
-    for (int u = 0; u < 7; ++u) {
-        const int c = 16 * u + r;
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int j = 16 * wv + 4 * g + reg;
-            if (c < kW) out[j * in_dim + c] = acc[u][reg];
-            else if (c == kW) out[ob1 + j] = acc[u][reg];
-            else if (c < kW + 1 + (in_dim - kW)) out[j * in_dim + c - 1] = acc[u][reg];
-        }
-    }
 }
 
 __device__ __forceinline__ float wave_sum(float v)
@@ -782,8 +583,6 @@ struct TdSet {
 };
 constexpr int kTdSetF = kSplitF + kHid * kLh + kHid;
 static_assert(kTdSetF == kTdSetF_, "LDS map");
-static_assert(2 * kW2hTerm / 2 <= kHid * kLh && kTile * kPsLd + 2 * kW2hTerm / 2 <= kTileF,
-              "fc2's f16 image fits where the f32 fc2 tile was (k_sac_td) and behind the packed rows in the critic phase's X area");
 constexpr size_t kSacTdLds = (size_t)(kSplitF + 2 * kTdSetF) * 4;      // actor layer 1 + both target critics: 120 KB
 __device__ __forceinline__ TdSet tdset_at(float *p)
 {
@@ -791,8 +590,6 @@ __device__ __forceinline__ TdSet tdset_at(float *p)
 }
 // critic fc1 (64 x 102: the two action columns -> scalar-block entries 16 / 17, b1 -> 15), fc2, b2 from the registers of
 // critic_issue; 256 threads
-// W2H: fc2 as the f16 image of layer2_fwd_h IN PLACE of the f32 tile (forward-only kernels: k_sac_td)
-template <bool W2H = false>
 __device__ __forceinline__ void critic_commit_split(const TdSet &S, const CritRegs &C)
 {
     const int tid = (int)threadIdx.x;
@@ -810,14 +607,10 @@ __device__ __forceinline__ void critic_commit_split(const TdSet &S, const CritRe
             }
         }
     }
-    if (W2H) {
-        layer2_commit_h(w2half_at(S.W2s), C);
-    } else {
 #pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int c = it * 256 + tid, row = c >> 4, q = c & 15;
-            *reinterpret_cast<floatx4 *>(S.W2s + row * kLh + 4 * q) = C.w2[it];
-        }
+    for (int it = 0; it < 4; ++it) {
+        const int c = it * 256 + tid, row = c >> 4, q = c & 15;
+        *reinterpret_cast<floatx4 *>(S.W2s + row * kLh + 4 * q) = C.w2[it];
     }
     if (tid < kHid) {
         float *d = S.W1.sc + tid * kScK;
@@ -825,17 +618,15 @@ __device__ __forceinline__ void critic_commit_split(const TdSet &S, const CritRe
         S.b2s[tid] = C.b2;
     }
 }
-// w2h: the 64 -> 64 layer from this f16 image (layer2_fwd_h) instead of S.W2s on the f32 pipe (nullptr)
 template <bool AHEAD = false>
 __device__ __forceinline__ void critic_fwd_split(const TdSet &S, const PRow &R, float a0, float a1, const W2Frag<2> &Fo,
-                                                 floatx4 (&acc1)[4], floatx4 (&acc2)[4], float (&q)[2], float *w2h = nullptr)
+                                                 floatx4 (&acc1)[4], floatx4 (&acc2)[4], float (&q)[2])
 {
     if (AHEAD) fwd_strip_split_ahead<true>(S.W1, R, acc1, a0, a1);
     else fwd_strip_split<true>(S.W1, R, acc1, a0, a1);
     floatx4 h1[4];
     relu4(acc1, h1);
-    if (w2h) layer2_fwd_h(w2half_at(w2h), S.b2s, h1, acc2);
-    else layer2_fwd(WSet{nullptr, S.W2s, S.b2s}, h1, acc2);
+    layer2_fwd(WSet{nullptr, S.W2s, S.b2s}, h1, acc2);
     q_strip<2>(acc2, Fo, 2, 2, 0, q);
 }
 
@@ -905,8 +696,8 @@ __global__ void __launch_bounds__(512) k_sac_td(SacArgsN slots)
         critic_issue(C1, g.t1);
         critic_issue(C2, g.t2);
         stage_actor_split(Wa, g.actor);
-        critic_commit_split<kSacW2Half>(S1, C1);
-        critic_commit_split<kSacW2Half>(S2, C2);
+        critic_commit_split(S1, C1);
+        critic_commit_split(S2, C2);
     }
     __syncthreads();
     for (int j = half; j < nt; j += 2) {
@@ -927,9 +718,9 @@ __global__ void __launch_bounds__(512) k_sac_td(SacArgsN slots)
         {   // (the two heads' fragments are re-read per use: 64 registers that two wavefronts per SIMD do not have; L1 hits)
             W2Frag<2> Fo;
             w2_load<2>(Fo, g.t1 + kCoWo, g.t1 + kCobo, 2);
-            critic_fwd_split(S1, T.R, a0, a1, Fo, acc, acc2, q1, kSacW2Half ? S1.W2s : nullptr);
+            critic_fwd_split(S1, T.R, a0, a1, Fo, acc, acc2, q1);
             w2_load<2>(Fo, g.t2 + kCoWo, g.t2 + kCobo, 2);
-            critic_fwd_split(S2, T.R, a0, a1, Fo, acc, acc2, q2, kSacW2Half ? S2.W2s : nullptr);
+            critic_fwd_split(S2, T.R, a0, a1, Fo, acc, acc2, q2);
         }
         if (gq < 2)                                // group d writes component d
             g.td[((size_t)(t0 + j) * kTile + 16 * wv + r) * 2 + d] =
@@ -1012,24 +803,19 @@ __global__ void __launch_bounds__(256) k_sac_critic_grad(SacArgsN slots)
         const float *flat = c ? g.c2 : g.c1;
         TileIn T;
         tile_in<false, true>(g, t0, T);
-        // (split dW1: the f32 X tile is gone, the packed rows take 1 792 of its 6 912 floats -- fc2's f16 image of layer2_fwd_h sits
-        // behind them; the backward keeps the f32 fc2 of SS)
-        float *w2h = (kSacSplitDw1 && kSacW2Half) ? Xs + kTile * kPsLd : nullptr;
+        // (split dW1: no f32 X tile, the packed rows take 1 792 of the X area's 6 912 floats)
         {
             CritRegs C;
             critic_issue(C, flat);
             critic_commit_split(SS, C);
-            if (w2h) layer2_commit_h(w2half_at(w2h), C);
         }
         W2Frag<2> Fo;
         w2_load<2>(Fo, flat + kCoWo, flat + kCobo, 2);
         __syncthreads();
         S_STAMP(3 + 6 * c);
-        floatx4 aw1[7], aw2[4], awo = floatx4{0.0f, 0.0f, 0.0f, 0.0f}, ab2 = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
+        floatx4 aw2[4], awo = floatx4{0.0f, 0.0f, 0.0f, 0.0f}, ab2 = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
         Dw1Split ws1;
         dw1_zero(ws1);
-#pragma unroll
-        for (int u = 0; u < 7; ++u) aw1[u] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int u = 0; u < 4; ++u) aw2[u] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
         float s_bo0 = 0.0f, s_bo1 = 0.0f, s_loss = 0.0f, s_cnt = 0.0f;
@@ -1039,7 +825,7 @@ __global__ void __launch_bounds__(256) k_sac_critic_grad(SacArgsN slots)
             const float *td = g.td ? g.td + ((size_t)(t0 + j) * kTile + 16 * wv + r) * 2 : tds + (j * kTile + 16 * wv + r) * 2;
             floatx4 acc1[4], acc2[4];
             float q[2];
-            critic_fwd_split<true>(SS, T.R, T.a0, T.a1, Fo, acc1, acc2, q, w2h);
+            critic_fwd_split<true>(SS, T.R, T.a0, T.a1, Fo, acc1, acc2, q);
             const float e0 = q[0] - td[0], e1 = q[1] - td[1];
             const float ww = T.w * T.isw;                                // validity x importance-sampling weight (1 without PER)
             const float dq0 = ww * e0 * inv_b, dq1 = ww * e1 * inv_b;    // d mean_{[B,2]}(w err^2) / dq = 2 w err / (2 B)
@@ -1056,17 +842,12 @@ __global__ void __launch_bounds__(256) k_sac_critic_grad(SacArgsN slots)
             h_strip_store(H2s, h2);
             h_strip_store(dH1s, dh1);
             h_strip_store(dH2s, dh2);
-            if (kSacSplitDw1) {
-                dh_strip_amax(dh1, red + 48);
-                if (gq == 0) ps_store(reinterpret_cast<uint32_t *>(Xs), 16 * wv + r, T.R, T.a0, T.a1);
-            } else {
-                x_strip_store(Xs, T.R, T.a0, T.a1);
-            }
+            dh_strip_amax(dh1, red + 48);
+            if (gq == 0) ps_store(reinterpret_cast<uint32_t *>(Xs), 16 * wv + r, T.R, T.a0, T.a1);
             if (gq == 0) { dqs[(16 * wv + r) * 4] = dq0; dqs[(16 * wv + r) * 4 + 1] = dq1; }
             __syncthreads();
             if (j == 0) S_STAMP(4 + 6 * c);
-            if (kSacSplitDw1) wgrad_x_split<true>(dH1s, reinterpret_cast<const uint32_t *>(Xs), red + 48, ws1);
-            else wgrad_xf(dH1s, Xs, aw1);              // dW1 (+ db1 as column 100)
+            wgrad_x_split<true>(dH1s, reinterpret_cast<const uint32_t *>(Xs), red + 48, ws1);     // dW1 (+ db1)
             if (j == 0) S_STAMP(5 + 6 * c);
             wgrad_critic_rest(dH2s, H1s, H2s, dqs, aw2, awo, ab2);     // dW2, dWout^T, db2
             __syncthreads();
@@ -1075,8 +856,7 @@ __global__ void __launch_bounds__(256) k_sac_critic_grad(SacArgsN slots)
         }
         S_STAMP(7 + 6 * c);
         float *out = g.partials + (size_t)blockIdx.x * kStrideC + c * kPc;
-        if (kSacSplitDw1) store_dw1_split<true>(out, kIn, kCob1, ws1);
-        else store_dw1(out, kIn, kCob1, aw1);
+        store_dw1_split<true>(out, kIn, kCob1, ws1);
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -1145,11 +925,9 @@ __global__ void __launch_bounds__(256) k_sac_actor_grad(SacArgsN slots)
     w2_load<2>(Fo1, g.c1 + kCoWo, g.c1 + kCobo, 2);
     w2_load<2>(Fo2, g.c2 + kCoWo, g.c2 + kCobo, 2);
     __syncthreads();
-    floatx4 aw1[7], awo = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
+    floatx4 awo = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
     Dw1Split ws1;
     dw1_zero(ws1);
-#pragma unroll
-    for (int u = 0; u < 7; ++u) aw1[u] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
     float s_b[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s_lp = 0.0f, s_loss = 0.0f, s_cnt = 0.0f;
     for (int j = 0; j < nt; ++j) {
         TileIn Tn = T;
@@ -1225,22 +1003,20 @@ __global__ void __launch_bounds__(256) k_sac_actor_grad(SacArgsN slots)
             }
         h_strip_store(H1s, h);
         h_strip_store(dH1s, dh);
-        if (kSacSplitDw1) dh_strip_amax(dh, red + 48);
+        dh_strip_amax(dh, red + 48);
         if (gq == 0) {
             ps_store(Ps, 16 * wv + r, T.R, 0.0f, 0.0f);
 #pragma unroll
             for (int a = 0; a < 4; ++a) { dqs[(16 * wv + r) * 4 + a] = dout[a]; s_b[a] += dout[a]; }
         }
         __syncthreads();
-        if (kSacSplitDw1) wgrad_x_split<false>(dH1s, Ps, red + 48, ws1);
-        else wgrad_x<false>(dH1s, Ps, aw1);
+        wgrad_x_split<false>(dH1s, Ps, red + 48, ws1);
         wgrad_small(H1s, dqs, 4, awo);
         __syncthreads();
         T = Tn;
     }
     float *out = g.partials + (size_t)blockIdx.x * kStrideA;
-    if (kSacSplitDw1) store_dw1_split<false>(out, kW, kHid * kW, ws1);
-    else store_dw1(out, kW, kHid * kW, aw1);
+    store_dw1_split<false>(out, kW, kHid * kW, ws1);
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg)
         if (r < 4) out[kAoW2 + r * kHid + 16 * wv + 4 * gq + reg] = awo[reg];
