@@ -270,9 +270,10 @@ __global__ void k_per_set_f32(UavPer p, const int64_t *__restrict__ slots, const
 // ReplayTree.sample's importance weights (:175-178): w_i = (n p_i / int(total)) ** -beta, then / max_i w_i.  Two launches:
 // the powers (one f64 pow per thread) with one maximum per workgroup, then the division by the maximum of those maxima
 // (fixed-order LDS trees: deterministic).  `w64` holds the unnormalised weights in between (it may alias the priorities),
-// `wg_max` one double per workgroup of the first launch.
-__global__ void __launch_bounds__(256) k_per_weights_pow(UavPer p, int n_chunks, const double *__restrict__ prio, int batch,
-                                                         double n_entries, double beta, double *__restrict__ w64,
+// `wg_max` one double per workgroup of the first launch.  (prio and w64 carry no __restrict__: uavenv_per_weights passes the same
+// buffer for both; each thread reads its priority before it writes its weight.)
+__global__ void __launch_bounds__(256) k_per_weights_pow(UavPer p, int n_chunks, const double *prio, int batch,
+                                                         double n_entries, double beta, double *w64,
                                                          double *__restrict__ wg_max)
 {
     __shared__ double red[256];
@@ -434,7 +435,8 @@ int uavenv_per_set_f32_gated(const UavPer *p, const int64_t *slots_dev, const fl
 int uavenv_per_weights(const UavPer *p, const int64_t *slots_dev, double *prio_dev, int32_t batch, int64_t n_entries,
                        double beta, int32_t n_agents, float *is_weights_out_dev, int32_t *frame_agent_out_dev, void *stream)
 {
-    if (!per_ok(p) || !slots_dev || !prio_dev || !is_weights_out_dev || batch <= 0 || n_entries < 0) return UAVENV_EINVAL;
+    // (n_entries <= 0: pow(0, -beta) = inf for every sample and inf / inf = NaN for the whole batch -- refused, see the header)
+    if (!per_ok(p) || !slots_dev || !prio_dev || !is_weights_out_dev || batch <= 0 || n_entries <= 0) return UAVENV_EINVAL;
     if (frame_agent_out_dev && n_agents <= 0) return UAVENV_EINVAL;
     const int n_wg = (batch + 255) / 256;
     double *wg_max = prio_dev + batch;                         // the scratch tail the caller left behind the priorities

@@ -342,7 +342,8 @@ int uavenv_per_set_f32_gated(const UavPer *per, const int64_t *slots_dev, const 
  * divided by their maximum (f32 out); a zero priority gets weight 0; int(total) < 1 counts as 1.  Also splits each slot
  * into the (frame, agent) pair uavenv_dqn_grad takes (frame_agent_out_dev nullable, batch x 2 int32; slot = frame *
  * n_agents + agent).  prio_dev: the batch priorities uavenv_per_sample returned FOLLOWED by (batch + 255) / 256 doubles of
- * scratch; the call overwrites all of it.  Needs the rebuild uavenv_per_sample used. */
+ * scratch; the call overwrites all of it.  Needs the rebuild uavenv_per_sample used.  n_entries <= 0 has no meaning (the
+ * reference never samples an empty tree, and 0 ** -beta would turn the whole batch into NaN): UAVENV_EINVAL, nothing is written. */
 int uavenv_per_weights(const UavPer *per, const int64_t *slots_dev, double *prio_dev, int32_t batch,
                        int64_t n_entries, double beta, int32_t n_agents, float *is_weights_out_dev,
                        int32_t *frame_agent_out_dev, void *stream);
