@@ -44,6 +44,7 @@ SYMBOLS = (
     "uavenv_sac_actor_adam", "uavenv_fed_aggregate", "uavenv_eval_episodes", "uavenv_eval_episodes_slots", "uavenv_eval_episodes_sac", "uavenv_eval_noise_fill",
     "uavenv_dqn_act_slots", "uavenv_replay_draw_slots", "uavenv_dqn_slots_loop_create", "uavenv_dqn_slots_loop_destroy",
     "uavenv_dqn_slots_loop_set_eps", "uavenv_dqn_slots_loop_run", "uavenv_dqn_slots_loop_get",
+    "uavenv_dqn_grad_slots", "uavenv_dqn_reduce_adam_slots", "uavenv_dqn_slots_loop_set_multi_update",
 )
 SAC_CRITIC_IN, SAC_ACTOR_PARAMS, SAC_CRITIC_PARAMS, SAC_ACTOR_STRIDE, SAC_CRITIC_STRIDE = 102, 6724, 10882, 6728, 21768
 
@@ -462,6 +463,22 @@ def load() -> C.CDLL:
     # (csrc/dqn_slots_internal.hpp: the form the slots loop calls, with one layer-1 image per net as an array of c_void_p)
     lib.uavenv_dqn_act_slots_img.restype = C.c_int
     lib.uavenv_dqn_act_slots_img.argtypes = [C.POINTER(C.POINTER(UavDqnNet)), i32, vp, i32, i32, f32, u64, u64, vp, vp, vp, vp]
+    # (arrays of n nets: nets as pointers to the structures; partials / loss cells / images / raw buckets as arrays of c_void_p,
+    # update counts and hard-copy flags as arrays of c_int32 -- all host memory)
+    nets_pp = C.POINTER(C.POINTER(UavDqnNet))
+    lib.uavenv_dqn_grad_slots.restype = C.c_int
+    lib.uavenv_dqn_grad_slots.argtypes = [C.POINTER(UavReplayRing), i32, i32, i32, u64, u64, vp, nets_pp, i32, i32, f32, i32, vp, vp]
+    lib.uavenv_dqn_grad_slots_img.restype = C.c_int
+    lib.uavenv_dqn_grad_slots_img.argtypes = [C.POINTER(UavReplayRing), i32, i32, i32, u64, u64, vp, nets_pp, i32, i32, f32, i32, vp,
+                                              vp, vp]
+    lib.uavenv_dqn_reduce_adam_slots.restype = C.c_int
+    lib.uavenv_dqn_reduce_adam_slots.argtypes = [nets_pp, i32, vp, i32, f32, f32, f32, f32, C.POINTER(i32), C.POINTER(i32), vp, vp,
+                                                 C.c_uint32, vp]
+    lib.uavenv_dqn_reduce_adam_slots_img.restype = C.c_int
+    lib.uavenv_dqn_reduce_adam_slots_img.argtypes = [nets_pp, i32, vp, i32, f32, f32, f32, f32, C.POINTER(i32), C.POINTER(i32), vp, vp,
+                                                     vp, C.c_uint32, vp, vp]
+    lib.uavenv_dqn_slots_loop_set_multi_update.restype = C.c_int
+    lib.uavenv_dqn_slots_loop_set_multi_update.argtypes = [vp, i32]
     lib.uavenv_replay_draw_slots.restype = C.c_int
     lib.uavenv_replay_draw_slots.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32, u64, u64, vp, vp]
     lib.uavenv_dqn_slots_loop_create.restype = C.c_int

@@ -1041,6 +1041,105 @@ __global__ void __launch_bounds__(512) k_dqn_grad_packed8(Grad2Args ga)
     }
 }
 
+// One learner per UAV slot in ONE launch: slice blockIdx.y of the grid is k_dqn_grad_packed8 for slot y -- its nets, its layer-1 image,
+// its (frame, agent) pairs, its partial rows, picked from the table in the kernel arguments by the wavefront-uniform blockIdx.y
+// (scalar loads: no VGPR holds a slot's pointer).  The ring and every hyper-parameter are the slots' common ones.  Same device
+// functions in the same order: workgroup (x, y) writes the row that workgroup x of k_dqn_grad_packed8 writes for slot y, bit for bit.
+// The kernel-level body (LDS carve-up, tile loop, partial-row writer) is k_dqn_grad_packed8's text again rather than a function both
+// call: with the body behind a call that kernel came out of the compiler with the same registers but another instruction stream, and
+// the single-learner loops are timed on it.
+constexpr int kActMaxSlots = 8;            // (= UAVENV_DQN_MAX_SLOTS: every per-slot table of kernel arguments)
+struct GradSlotsArgs {
+    Grad2Args ga;                    // g.local / target / img / partials / explicit_idx are taken from slot[] below; no is_w / abs_td / dbg
+    struct { const float *local, *target, *img; float *partials; const int32_t *pairs; } slot[kActMaxSlots];
+};
+
+template <bool GLDS>
+__global__ void __launch_bounds__(512) k_dqn_grad_slots(GradSlotsArgs sa)
+{
+    UAV_HOT_PRIO();
+    const int y = (int)blockIdx.y;
+    GradArgs g = sa.ga.g;
+    g.local = sa.slot[y].local;
+    g.target = sa.slot[y].target;
+    g.img = sa.slot[y].img;
+    g.partials = sa.slot[y].partials;
+    g.explicit_idx = sa.slot[y].pairs;
+    // the pairs are mandatory and there are no sample weights, |TD| outputs or phase stamps in this form: known here, so that the
+    // draw and those branches (and the scalar registers their arguments would hold) are not compiled in
+    __builtin_assume(g.explicit_idx != nullptr);
+    g.is_w = nullptr;
+    g.abs_td = nullptr;
+    g.dbg = nullptr;
+    const Grad2Args &ga = sa.ga;
+    constexpr int NMAX = 4;
+    extern __shared__ __align__(16) float lds[];
+    GradLdsP L;
+    L.W1l = lds;
+    L.W1t = L.W1l + kTileF;
+    L.Hs = L.W1t + kTileF;
+    L.dHs = L.Hs + kTile * kLh;
+    L.douts = L.dHs + kTile * kLh;
+    L.W2l = L.douts + kTile * kMaxOut;
+    L.W2t = L.W2l + kMaxOut * kHid;
+    L.b2l = L.W2t + kMaxOut * kHid;
+    L.b2t = L.b2l + kMaxOut;
+    L.red = L.b2t + kMaxOut;
+    L.Ps = reinterpret_cast<uint32_t *>(L.red + 4 * (kMaxOut + 2));
+    float *qn_lds = reinterpret_cast<float *>(L.Ps + kTile * kPackedDwords + 4);
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), grp = wv >> 2, strip = wv & 3;
+    const int r = lane & 15, gq = lane >> 4;
+    const int n2 = g.n_actions + (g.dueling ? 1 : 0);
+    GradAcc8 A;
+#pragma unroll
+    for (int u = 0; u < 6; ++u) A.acc[u] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int a = 0; a < 6; ++a) A.csum[a] = 0.0f;
+    L_STAMP(0);
+    const int step = (int)gridDim.x;
+    int tile = (int)blockIdx.x;
+    grad_tile_packed8<true, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
+    for (tile += step; tile < ga.n_tiles; tile += step)
+        grad_tile_packed8<false, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
+    L_STAMP(5);
+    // ---- the partial-gradient row of this workgroup: dW1 | db1 | dW2 | db2 | loss sum | valid count
+    float *out = g.partials + (size_t)blockIdx.x * ga.stride;
+    const int oW2 = kHid * kW + kHid, ob2 = oW2 + n2 * kHid;
+    const int j = 16 * strip + r;
+    // (grad_products_split8's register layout) group 1: acc[u] = tile u of the flag columns (exact zeros at the scalar columns, which
+    // group 0 stores from its gathered tile: columns 0..10 and 86..89 are left out here); group 0: acc[0] = the gathered tile
+    // (entries 0..10 = columns 0..10, 11..14 = 86..89, 15 = db1), acc[1] = dW2^T; columns 96..99 are constant zero
+    if (grp == 1) {
+        float *t0 = out + j * kW + 4 * gq;
+        if (gq == 3) UAV_ROW_ST4(t0, A.acc[0]);                      // columns 12..15
+        else if (gq == 2) t0[3] = A.acc[0][3];                       // column 11
+#pragma unroll
+        for (int u = 1; u < 5; ++u) UAV_ROW_ST4(out + j * kW + 16 * u + 4 * gq, A.acc[u]);
+        float *t5 = out + j * kW + 80 + 4 * gq;
+        if (gq == 0 || gq == 3) UAV_ROW_ST4(t5, A.acc[5]);
+        else if (gq == 1) { t5[0] = A.acc[5][0]; t5[1] = A.acc[5][1]; }
+        else { t5[2] = A.acc[5][2]; t5[3] = A.acc[5][3]; }
+    } else {
+        const floatx4 sc = A.acc[0];
+        if (gq < 2) UAV_ROW_ST4(out + j * kW + 4 * gq, sc);                                            // columns 0..7
+        else if (gq == 2) { out[j * kW + 8] = sc[0]; out[j * kW + 9] = sc[1]; out[j * kW + 10] = sc[2]; out[j * kW + 86] = sc[3]; }
+        else { out[j * kW + 87] = sc[0]; out[j * kW + 88] = sc[1]; out[j * kW + 89] = sc[2]; out[kHid * kW + j] = sc[3]; }
+        if (gq == 0) UAV_ROW_ST4(out + j * kW + 96, (floatx4{0.0f, 0.0f, 0.0f, 0.0f}));
+        if (r < n2) UAV_ROW_ST4(out + oW2 + r * kHid + 16 * strip + 4 * gq, A.acc[1]);                  // dW2^T
+    }
+    if (grp == 0 && lane == 0) {
+#pragma unroll
+        for (int a = 0; a < NMAX + 2; ++a) L.red[strip * (kMaxOut + 2) + a] = A.csum[a];
+    }
+    __syncthreads();
+    if (tid < NMAX + 2) {
+        const float s = (L.red[tid] + L.red[(kMaxOut + 2) + tid]) + (L.red[2 * (kMaxOut + 2) + tid] + L.red[3 * (kMaxOut + 2) + tid]);
+        if (tid < n2) out[ob2 + tid] = s;
+        else if (tid == NMAX) out[g.P] = s;
+        else if (tid == NMAX + 1) out[g.P + 1] = s;
+    }
+}
+
 constexpr size_t kGradP8Lds = (size_t)(2 * kTileF + 2 * kTile * kLh + kTile * kMaxOut + 2 * kMaxOut * kHid + 2 * kMaxOut +
                                        4 * (kMaxOut + 2) + kTile * kPackedDwords + 4 + kTile + 4) * 4;      // (+ 4: the strips' max |dH|)
 
@@ -1607,6 +1706,70 @@ __global__ void __launch_bounds__(256) k_dqn_reduce_adam(const float *__restrict
     }
 }
 
+// The same for one learner per UAV slot in ONE launch: slice blockIdx.y of the grid is k_dqn_reduce_adam for slot y (its partial rows,
+// blocks, loss cell, image, bias corrections and hard-copy flag from the table; the slots' update counts may differ).  Same summation
+// order (reduce_columns), same Adam arithmetic: bit for bit the per-slot launch.  One gate for all slots.
+struct AdamSlotsArgs {
+    int nblk, P, stride;
+    float lr, beta1, beta2, eps;
+    const uint32_t *go_word;
+    uint32_t go_value;
+    struct {
+        const float *partials;
+        float *local, *target, *m, *v, *loss, *raw, *img;    // loss, raw, img nullable
+        float bc1, bc2_sqrt;
+        int hard_update;
+    } slot[kActMaxSlots];
+};
+
+__global__ void __launch_bounds__(256) k_dqn_reduce_adam_slots(AdamSlotsArgs a)
+{
+    const auto &sl = a.slot[blockIdx.y];
+    const float *__restrict__ partials = sl.partials;
+    float *__restrict__ local = sl.local, *__restrict__ target = sl.target, *__restrict__ m = sl.m, *__restrict__ v = sl.v;
+    float *__restrict__ loss = sl.loss, *__restrict__ raw = sl.raw, *__restrict__ img = sl.img;
+    const uint32_t *__restrict__ go_word = a.go_word;
+    const uint32_t go_value = a.go_value;
+    const int nblk = a.nblk, P = a.P, stride = a.stride, hard_update = sl.hard_update;
+    const float lr = a.lr, beta1 = a.beta1, beta2 = a.beta2, eps = a.eps, bc1 = sl.bc1, bc2_sqrt = sl.bc2_sqrt;
+    // (from here k_dqn_reduce_adam's text: that kernel stays as the compiler made it, see k_dqn_grad_slots)
+    UAV_HOT_PRIO();
+    if (go_word && __hip_atomic_load(go_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != go_value) return;
+    __shared__ float cnt_part[4];
+    const int tid = (int)threadIdx.x;
+    const int p = (int)blockIdx.x * 32 + tid;
+    // this parameter's moments and value are requested FIRST: their round trip runs under the partial rows' (behind the
+    // reduction's barriers they were a second, dependent round trip of the launch)
+    float m0 = 0.0f, v0 = 0.0f, w0 = 0.0f;
+    if (tid < 32 && p < P) { m0 = m[p]; v0 = v[p]; w0 = local[p]; }
+    float c;
+    const float t = reduce_columns(partials, nblk, P, stride, c);
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    if ((tid & 63) == 0) cnt_part[tid >> 6] = c;
+    __syncthreads();
+    const float cnt = (cnt_part[0] + cnt_part[1]) + (cnt_part[2] + cnt_part[3]);
+    const float inv = 1.0f / (cnt > 1.0f ? cnt : 1.0f);
+    if (tid < 32 && p < P + 2) {
+        if (raw) raw[p] = t;
+        if (p < P) {
+            const float gp = t * inv;
+            const float mp = m0 + (gp - m0) * (1.0f - beta1);
+            const float vp = v0 * beta2 + (1.0f - beta2) * gp * gp;
+            m[p] = mp;
+            v[p] = vp;
+            const float np = w0 - (lr / bc1) * (mp / (sqrtf(vp) / bc2_sqrt + eps));
+            local[p] = np;
+            if (hard_update) target[p] = np;
+            if (img) {                        // the C loop's layer-1 image follows the parameters (qnet_device.hpp: img_store_param)
+                img_store_param(img, p, np);
+                if (hard_update) img_store_param(img + kSplitF, p, np);
+            }
+        } else if (p == P && loss) {
+            *loss = t * inv;
+        }
+    }
+}
+
 struct ActArgs {
     const void *obs;       // [n][100]
     int n, n_actions, dueling;
@@ -1760,7 +1923,6 @@ __global__ void __launch_bounds__(256) k_dqn_act_packed(ActArgs g)
 // the grid stages net y and a lane's env e reads packed row e * U + y.  Same device functions in the same order, so the Q row and
 // the action of agent e * U + y are bit for bit those of k_dqn_act_packed with net y on slot y's rows gathered contiguously, under
 // the key seed + y (the draw is keyed by the env, as there).
-constexpr int kActMaxSlots = 8;
 struct ActSlotsArgs {
     const void *obs;       // [n_envs * n_nets][20 dwords]
     int n_envs, n_nets, n_actions, dueling;
@@ -2012,6 +2174,20 @@ static int launch_grad_packed8(const Grad2Args &ga, int grid, hipStream_t s)
         attr = true;
     }
     hipLaunchKernelGGL((k_dqn_grad_packed8<GLDS>), dim3(grid), dim3(512), kGradP8Lds, s, ga);
+    return UAVENV_OK;
+}
+
+template <bool GLDS>
+static int launch_grad_slots(const GradSlotsArgs &sa, int grid, int n_nets, hipStream_t s)
+{
+    static bool attr = false;
+    if (!attr) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_slots<GLDS>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess)
+            return UAVENV_EHIP;
+        attr = true;
+    }
+    hipLaunchKernelGGL((k_dqn_grad_slots<GLDS>), dim3(grid, n_nets), dim3(512), kGradP8Lds, s, sa);
     return UAVENV_OK;
 }
 
@@ -2275,6 +2451,115 @@ int uavenv_dqn_act_slots(const UavDqnNet *const *nets, int32_t n_nets, const voi
 {
     return uavenv_dqn_act_slots_img(nets, n_nets, obs_dev, obs_dtype, n_envs, eps, seed, counter, index_out_dev, q_out_dev, nullptr,
                                     stream);
+}
+
+// (internal, csrc/dqn_slots_internal.hpp) images: n_nets pointers (host array, nullable as a whole and per net) to uavenv_dqn_split_image's
+// output for net j as it is now.  Everything is checked before anything is enqueued.
+int uavenv_dqn_grad_slots_img(const UavReplayRing *ring, int32_t head, int32_t filled, int32_t batch, uint64_t seed, uint64_t counter,
+                              const int32_t *pairs_dev, const UavDqnNet *const *nets, int32_t n_nets, int32_t kind, float gamma,
+                              int32_t huber, float *const *partials, const float *const *images, void *stream)
+{
+    if (!nets || !partials || !pairs_dev || n_nets < 1 || n_nets > kActMaxSlots) return UAVENV_EINVAL;
+    if (!ring || !ring->obs || !ring->action || !ring->reward || !ring->done || ring->obs_dtype != UAVENV_OBS_PACKED) return UAVENV_EINVAL;
+    if (batch <= 0 || batch % kTile != 0 || ring->frames < 2 || head < 0 || head >= ring->frames) return UAVENV_EINVAL;
+    if ((uint64_t)ring->frames * (uint64_t)ring->n_agents >= (1ull << 32) || !ring->action_is_index) return UAVENV_EINVAL;
+    if ((((uintptr_t)ring->meta) & 15u) != 0 || (((uintptr_t)pairs_dev) & 7u) != 0) return UAVENV_EINVAL;
+    GradSlotsArgs sa;
+    bool all_img = true;
+    for (int j = 0; j < kActMaxSlots; ++j) sa.slot[j] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int j = 0; j < n_nets; ++j) {
+        const UavDqnNet *n = nets[j];
+        if (!net_ok(n) || !n->target || !partials[j] || n->mfma_dtype != UAVENV_MFMA_F32) return UAVENV_EINVAL;
+        if (n->n_actions + (n->dueling ? 1 : 0) > 4) return UAVENV_EINVAL;                       // the packed8 family only
+        if (n->n_actions != nets[0]->n_actions || (n->dueling != 0) != (nets[0]->dueling != 0)) return UAVENV_EINVAL;
+        if ((((uintptr_t)partials[j] | (uintptr_t)n->local | (uintptr_t)n->target) & 15u) != 0) return UAVENV_EINVAL;
+        for (int i = 0; i < j; ++i)
+            if (nets[i]->local == n->local || partials[i] == partials[j]) return UAVENV_EINVAL;
+        const float *im = images ? images[j] : nullptr;
+        sa.slot[j].local = n->local;
+        sa.slot[j].target = n->target;
+        sa.slot[j].img = (im && (((uintptr_t)im) & 15u) == 0) ? im : nullptr;       // (as uavenv_dqn_grad_img: such a net converts for itself)
+        sa.slot[j].partials = partials[j];
+        sa.slot[j].pairs = pairs_dev + (size_t)j * (size_t)batch * 2;
+        all_img = all_img && sa.slot[j].img;
+    }
+    GradArgs &g = sa.ga.g;
+    g.ring = *ring;
+    g.head = head; g.filled = filled; g.batch = batch;
+    g.seed = seed; g.counter = counter;
+    g.explicit_idx = pairs_dev;
+    g.perm = replay_perm(seed, counter, 1u, (uint32_t)ring->n_agents);
+    g.local = nullptr; g.target = nullptr; g.partials = nullptr; g.img = nullptr;
+    g.n_actions = nets[0]->n_actions; g.dueling = nets[0]->dueling; g.kind = kind;
+    g.gamma = gamma; g.huber = huber;
+    g.P = uavenv_dqn_num_params(nets[0]);
+    g.dbg = nullptr;
+    g.is_w = nullptr;
+    g.abs_td = nullptr;
+    sa.ga.n_tiles = batch / kTile;
+    sa.ga.stride = uavenv_dqn_partial_stride(nets[0]);
+    const int grid = uavenv_dqn_partial_rows(batch);
+    // every slot with an image: both layer-1 images by LDS-DMA, as uavenv_dqn_grad_img stages them (UAVENV_STAGE_VGPR=1 keeps the
+    // register-staged form); otherwise the register-staged kernel, in which a slot without an image converts fc1 -- same values
+    static const bool stage_vgpr = getenv("UAVENV_STAGE_VGPR") && atoi(getenv("UAVENV_STAGE_VGPR")) != 0;
+    const int rc = all_img && !stage_vgpr ? launch_grad_slots<true>(sa, grid, n_nets, (hipStream_t)stream)
+                                          : launch_grad_slots<false>(sa, grid, n_nets, (hipStream_t)stream);
+    if (rc != UAVENV_OK) return rc;
+    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+}
+
+int uavenv_dqn_grad_slots(const UavReplayRing *ring, int32_t head, int32_t filled, int32_t batch, uint64_t seed, uint64_t counter,
+                          const int32_t *pairs_dev, const UavDqnNet *const *nets, int32_t n_nets, int32_t kind, float gamma,
+                          int32_t huber, float *const *partials, void *stream)
+{
+    return uavenv_dqn_grad_slots_img(ring, head, filled, batch, seed, counter, pairs_dev, nets, n_nets, kind, gamma, huber, partials,
+                                     nullptr, stream);
+}
+
+// (internal, csrc/dqn_slots_internal.hpp) raw_out: n_nets pointers (host array, nullable as a whole and per net) receiving slot j's
+// column sums as uavenv_dqn_reduce_adam's raw_out; images: as above, kept current with the new parameters
+int uavenv_dqn_reduce_adam_slots_img(const UavDqnNet *const *nets, int32_t n_nets, float *const *partials, int32_t n_partials,
+                                     float lr, float beta1, float beta2, float eps, const int32_t *step_t, const int32_t *hard_update,
+                                     float *const *loss_out, float *const *raw_out, const uint32_t *go_word_dev, uint32_t go_value,
+                                     float *const *images, void *stream)
+{
+    if (!nets || !partials || !step_t || !hard_update || n_nets < 1 || n_nets > kActMaxSlots || n_partials <= 0) return UAVENV_EINVAL;
+    AdamSlotsArgs a;
+    for (int j = 0; j < kActMaxSlots; ++j) a.slot[j] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f, 1.0f, 0};
+    for (int j = 0; j < n_nets; ++j) {
+        const UavDqnNet *n = nets[j];
+        float *im = images ? images[j] : nullptr;
+        if (!net_ok(n) || !n->target || !n->m || !n->v || !partials[j] || step_t[j] <= 0) return UAVENV_EINVAL;
+        if (im && (n->w != kW || n->hid != kHid || (((uintptr_t)im) & 15u) != 0)) return UAVENV_EINVAL;
+        if (n->n_actions != nets[0]->n_actions || (n->dueling != 0) != (nets[0]->dueling != 0)) return UAVENV_EINVAL;
+        if ((((uintptr_t)partials[j]) & 15u) != 0) return UAVENV_EINVAL;
+        for (int i = 0; i < j; ++i)
+            if (nets[i]->local == n->local || partials[i] == partials[j]) return UAVENV_EINVAL;
+        const float bc2 = 1.0f - powf(beta2, (float)step_t[j]);
+        a.slot[j].partials = partials[j];
+        a.slot[j].local = n->local; a.slot[j].target = n->target; a.slot[j].m = n->m; a.slot[j].v = n->v;
+        a.slot[j].loss = loss_out ? loss_out[j] : nullptr;
+        a.slot[j].raw = raw_out ? raw_out[j] : nullptr;
+        a.slot[j].img = im;
+        a.slot[j].bc1 = 1.0f - powf(beta1, (float)step_t[j]);
+        a.slot[j].bc2_sqrt = sqrtf(bc2);
+        a.slot[j].hard_update = hard_update[j];
+    }
+    a.P = uavenv_dqn_num_params(nets[0]);
+    a.nblk = n_partials;
+    a.stride = uavenv_dqn_partial_stride(nets[0]);
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+    a.go_word = go_word_dev; a.go_value = go_value;
+    hipLaunchKernelGGL(k_dqn_reduce_adam_slots, dim3((a.P + 2 + 31) / 32, n_nets), dim3(256), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+}
+
+int uavenv_dqn_reduce_adam_slots(const UavDqnNet *const *nets, int32_t n_nets, float *const *partials, int32_t n_partials, float lr,
+                                 float beta1, float beta2, float eps, const int32_t *step_t, const int32_t *hard_update,
+                                 float *const *loss_out, const uint32_t *go_word_dev, uint32_t go_value, void *stream)
+{
+    return uavenv_dqn_reduce_adam_slots_img(nets, n_nets, partials, n_partials, lr, beta1, beta2, eps, step_t, hard_update, loss_out,
+                                            nullptr, go_word_dev, go_value, nullptr, stream);
 }
 
 }  // extern "C"

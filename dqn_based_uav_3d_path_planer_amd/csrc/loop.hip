@@ -702,6 +702,7 @@ int uavenv_sac_loop_run(UavSacLoop *l, int32_t n_steps, void *stream)
 //     uavenv_step                   Move_Agent for every agent, replay write included
 //     uavenv_replay_draw_slots      (frame, agent) pairs for all slots at once
 //     U x (uavenv_dqn_grad, uavenv_dqn_reduce_adam)       learn_off_policy of slot j on ITS rows
+//         -- or, with uavenv_dqn_slots_loop_set_multi_update, uavenv_dqn_grad_slots + uavenv_dqn_reduce_adam_slots: all slots in two launches
 // Driven from Python this is, per pass and slot, a strided gather, uavenv_dqn_act and a scatter, then the step, then per slot a
 // draw, the gradient and Adam.  Every launch goes through the library's own entry points: K passes from here == K passes of
 // the caller issuing them, bit for bit.  A struct of its own beside UavLoop: that one already serves prioritised replay, the
@@ -718,6 +719,8 @@ struct UavDqnSlotsLoop {
     // fc1 / b1 of every slot's q_local and q_target in the split form (UavLoop.img has the story): n_slots buffers of
     // 2 x UAVENV_DQN_IMAGE_FLOATS, rebuilt when a run starts, kept current by the loop's own Adam launches
     float *img = nullptr;
+    // uavenv_dqn_slots_loop_set_multi_update: the learning phase as one gradient and one Adam launch for all slots
+    int32_t multi_update = 0;
 };
 
 extern "C" {
@@ -778,6 +781,15 @@ int uavenv_dqn_slots_loop_set_eps(UavDqnSlotsLoop *l, float eps)
     return UAVENV_OK;
 }
 
+int uavenv_dqn_slots_loop_set_multi_update(UavDqnSlotsLoop *l, int32_t on)
+{
+    if (!l) return UAVENV_EINVAL;
+    const UavDqnNet &n0 = l->c.slot[0].net;
+    if (on && n0.n_actions + (n0.dueling ? 1 : 0) > 4) return UAVENV_EINVAL;      // uavenv_dqn_grad_slots: the packed8 family only
+    l->multi_update = on ? 1 : 0;
+    return UAVENV_OK;
+}
+
 int uavenv_dqn_slots_loop_get(const UavDqnSlotsLoop *l, UavDqnSlotsLoopCursor *out)
 {
     if (!l || !out) return UAVENV_EINVAL;
@@ -828,16 +840,33 @@ int uavenv_dqn_slots_loop_run(UavDqnSlotsLoop *l, int32_t n_steps, void *stream)
                                           c.seed + 7, l->counter, c.draws_dev, s);
             if (rc != UAVENV_OK) return rc;
             const int rows = uavenv_dqn_partial_rows(B);
-            for (int j = 0; j < U; ++j) {
-                const UavDqnSlotsLoopSlot &sl = c.slot[j];
-                rc = uavenv_dqn_grad_img(&R, l->head, l->filled, B, c.seed, l->counter, c.draws_dev + (size_t)j * B * 2, nets[j], c.kind,
-                                         c.gamma, c.huber, nullptr, nullptr, sl.partials_dev, img[j], s);
+            if (l->multi_update) {            // all slots' updates in one gradient and one Adam launch: same results
+                float *partials[UAVENV_DQN_MAX_SLOTS], *loss[UAVENV_DQN_MAX_SLOTS];
+                int32_t step_t[UAVENV_DQN_MAX_SLOTS], hard[UAVENV_DQN_MAX_SLOTS];
+                for (int j = 0; j < U; ++j) { partials[j] = c.slot[j].partials_dev; loss[j] = c.slot[j].loss_dev; }
+                rc = uavenv_dqn_grad_slots_img(&R, l->head, l->filled, B, c.seed, l->counter, c.draws_dev, nets, U, c.kind, c.gamma,
+                                               c.huber, partials, img, s);
+                if (rc != UAVENV_OK) return rc;           // (no epoch has moved)
+                for (int j = 0; j < U; ++j) {
+                    l->epoch[j] += 1;
+                    step_t[j] = l->epoch[j];
+                    hard[j] = l->epoch[j] % c.update_loop == 0 ? 1 : 0;
+                }
+                rc = uavenv_dqn_reduce_adam_slots_img(nets, U, partials, rows, c.lr, c.beta1, c.beta2, c.adam_eps, step_t, hard, loss,
+                                                      nullptr, c.moved_dev, (uint32_t)uavenv_tick(c.env), img, s);
                 if (rc != UAVENV_OK) return rc;
-                l->epoch[j] += 1;
-                const int hard = l->epoch[j] % c.update_loop == 0 ? 1 : 0;
-                rc = uavenv_dqn_reduce_adam_img(nets[j], sl.partials_dev, rows, c.lr, c.beta1, c.beta2, c.adam_eps, l->epoch[j], hard,
-                                                sl.loss_dev, nullptr, c.moved_dev, (uint32_t)uavenv_tick(c.env), img[j], s);
-                if (rc != UAVENV_OK) return rc;
+            } else {
+                for (int j = 0; j < U; ++j) {
+                    const UavDqnSlotsLoopSlot &sl = c.slot[j];
+                    rc = uavenv_dqn_grad_img(&R, l->head, l->filled, B, c.seed, l->counter, c.draws_dev + (size_t)j * B * 2, nets[j],
+                                             c.kind, c.gamma, c.huber, nullptr, nullptr, sl.partials_dev, img[j], s);
+                    if (rc != UAVENV_OK) return rc;
+                    l->epoch[j] += 1;
+                    const int hard = l->epoch[j] % c.update_loop == 0 ? 1 : 0;
+                    rc = uavenv_dqn_reduce_adam_img(nets[j], sl.partials_dev, rows, c.lr, c.beta1, c.beta2, c.adam_eps, l->epoch[j],
+                                                    hard, sl.loss_dev, nullptr, c.moved_dev, (uint32_t)uavenv_tick(c.env), img[j], s);
+                    if (rc != UAVENV_OK) return rc;
+                }
             }
         }
         l->counter += 1;

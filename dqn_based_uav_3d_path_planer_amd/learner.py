@@ -606,3 +606,50 @@ def act_slots(learners, obs: torch.Tensor, eps: float, seed: int, counter: int, 
         rc = lib.uavenv_dqn_act_slots_img(nets, U, obs.data_ptr(), _lib.OBS_PACKED, N // U, float(eps), int(seed) & (2 ** 64 - 1),
                                           int(counter), index_out.data_ptr(), qp, imgs, s)
     _lib.check(rc, "uavenv_dqn_act_slots")
+
+
+def update_slots(learners, ring, batch: int, pairs: torch.Tensor, images=None):
+    """One learn_off_policy() of every UAV slot's learner in TWO launches (uavenv_dqn_grad_slots, uavenv_dqn_reduce_adam_slots):
+    learners[j] trains on ITS `batch` (frame, agent) pairs pairs[j] of the packed ring -- bit for bit what
+    learners[j].learn_from_ring(ring, batch, 0, 0, explicit_idx=pairs[j]) gives: flat blocks, epoch, loss (each learner's own
+    `loss` cell).  pairs: contiguous int32 [U, batch, 2] on the device (DeviceReplayRing.draw_slots' layout).  images: one
+    split_image() tensor per learner (or None) -- the form the slots loop launches; they follow the new parameters."""
+    import ctypes as C
+    from . import _lib
+    ls = check_slot_learners(learners)
+    U, L0 = len(ls), ls[0]
+    hyper = lambda L: (L.kind, L.huber, L.update_loop, L.gamma, L.lr, tuple(L.betas), L.eps)
+    for L in ls:             # one Trainer.xml: the slots share kind and hyper-parameters
+        if hyper(L) != hyper(L0):
+            raise ValueError("the slots' learners must share their kind and hyper-parameters")
+    if int(batch) <= 0 or int(batch) % 64:
+        raise ValueError("fused learner needs batch % 64 == 0")
+    if pairs is None or pairs.dtype != torch.int32 or tuple(pairs.shape) != (U, int(batch), 2) or not pairs.is_contiguous():
+        raise ValueError("pairs must be a contiguous int32 [U, batch, 2] tensor")
+    if not ring.discrete or not ring.env.packed:
+        raise ValueError("update_slots learns from a discrete (DQN-family) packed ring")
+    if images is not None and len(images) != U:
+        raise ValueError("images: one per learner")
+    if not pairs.is_cuda:
+        raise ValueError("pairs must be on the device")
+    lib = _lib.load()
+    batch = int(batch)
+    nblk = lib.uavenv_dqn_partial_rows(batch)
+    for L in ls:
+        if L._partials is None or L._partials.shape[0] != nblk:
+            L._partials = L.new_partials(batch)
+    nets = (C.POINTER(_lib.UavDqnNet) * U)(*[C.pointer(L.net) for L in ls])
+    parts = (C.c_void_p * U)(*[L._partials.data_ptr() for L in ls])
+    imgs = None if images is None else (C.c_void_p * U)(*[None if t is None else t.data_ptr() for t in images])
+    s = torch.cuda.current_stream(pairs.device).cuda_stream
+    rc = lib.uavenv_dqn_grad_slots_img(C.byref(ring._c), ring.head, ring.filled, batch, 0, 0, pairs.data_ptr(), nets, U,
+                                       0 if L0.kind == "dqn" else 1, L0.gamma, L0.huber, parts, imgs, s)
+    _lib.check(rc, "uavenv_dqn_grad_slots")
+    for L in ls:
+        L.epoch += 1
+    steps = (C.c_int32 * U)(*[L.epoch for L in ls])
+    hard = (C.c_int32 * U)(*[1 if L.epoch % L.update_loop == 0 else 0 for L in ls])
+    loss = (C.c_void_p * U)(*[L.loss.data_ptr() for L in ls])
+    rc = lib.uavenv_dqn_reduce_adam_slots_img(nets, U, parts, nblk, L0.lr, L0.betas[0], L0.betas[1], L0.eps, steps, hard, loss, None,
+                                              None, 0, imgs, s)
+    _lib.check(rc, "uavenv_dqn_reduce_adam_slots")

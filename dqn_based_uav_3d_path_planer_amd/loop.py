@@ -348,17 +348,18 @@ class SACHotLoop:
 class DQNSlotsHotLoop:
     """The off-policy loop with one fused DQN-family learner per UAV slot (Envs/PathPlan_City.py:59-69, :364-385), enqueued by
     csrc/loop.hip: per pass ONE act launch for all slots (uavenv_dqn_act_slots), the env step (replay write included), ONE draw
-    of (frame, agent) pairs for all slots and per slot the gradient and Adam launches -- what the general run_eposide issues
-    from Python slot by slot, without the interpreter between the launches.  Uniform replay on one GPU.  The ring cursor and the
+    of (frame, agent) pairs for all slots and per slot the gradient and Adam launches (with multi_update: one of each for all
+    slots) -- what the general run_eposide issues from Python slot by slot, without the interpreter between the launches.  Uniform replay on one GPU.  The ring cursor and the
     learners' update counts live in the C object while the loop exists; `run` writes them back.  The learners' parameters may
     be replaced between two runs (a federated merge): every run rebuilds the layer-1 images its launches stage."""
 
     def __init__(self, ring: DeviceReplayRing, learners, batch: int, seed: int, eps: float = 0.1, counter: int = 0,
                  learn_start: int = 0, auto_reset: bool = True, skip_done: bool = True, info: torch.Tensor = None,
-                 gate_updates: bool = False, valid_draws: bool = None):
+                 gate_updates: bool = False, valid_draws: bool = None, multi_update: bool = False):
         """valid_draws (default: on when finished agents are skipped and not restarted): the draws go over the valid rows only
         (the reference never stores a row for a finished agent, Envs/PathPlan_City.py:456-459); gate_updates: no update of any
-        slot behind a step that moved nobody (HotLoop has the story)."""
+        slot behind a step that moved nobody (HotLoop has the story); multi_update: all slots' updates of a pass in one gradient
+        and one Adam launch (uavenv_dqn_grad_slots, uavenv_dqn_reduce_adam_slots) -- same results, 5 launches per pass."""
         from .learner import check_slot_learners
         # every check on the Python objects first: nothing below this block fails for a reason the caller could have known
         if not ring.discrete or not ring.env.packed:
@@ -410,6 +411,9 @@ class DQNSlotsHotLoop:
         self._keep = info
         self._h = C.c_void_p()
         _lib.check(self.lib.uavenv_dqn_slots_loop_create(C.byref(cfg), C.byref(self._h)), "uavenv_dqn_slots_loop_create")
+        self.multi_update = False
+        if multi_update:
+            self.set_multi_update(True)
         self.counter = int(counter)
         self.batch = int(batch)
         self._seen = (ring.head, ring.filled, tuple(L.epoch for L in ls))
@@ -433,6 +437,11 @@ class DQNSlotsHotLoop:
 
     def set_eps(self, eps: float):
         _lib.check(self.lib.uavenv_dqn_slots_loop_set_eps(self._h, float(eps)), "uavenv_dqn_slots_loop_set_eps")
+
+    def set_multi_update(self, on: bool):
+        """From the next run: the slots' updates in one gradient and one Adam launch (True) or slot by slot (False)."""
+        _lib.check(self.lib.uavenv_dqn_slots_loop_set_multi_update(self._h, 1 if on else 0), "uavenv_dqn_slots_loop_set_multi_update")
+        self.multi_update = bool(on)
 
     def run(self, n_steps: int):
         """Enqueue n_steps passes on the current torch stream (asynchronous)."""

@@ -616,7 +616,9 @@ class PathPlan_City:
         """run_eposide with one fused DQN-family trainer per UAV slot (<fused_slots>1</fused_slots>, num_UAV > 1):
         DQNSlotsHotLoop enqueues done_check passes at a time -- one act launch for all slots on the packed rows of the current
         frame, the env step (replay write included), one draw of every slot's Batch_Size transitions over ITS valid rows, and
-        per slot the gradient and Adam launches (:364-385, :456).  The host reads back, every done_check passes, how many agents
+        one gradient and one Adam launch for all slots (:364-385, :456; multi_update: measured faster than the per-slot launches
+        at both shapes of profiles/dqn_slots_update_times.json, bit-identical results; heads of more than 4 layer-2 outputs keep
+        the per-slot launches, the only form that takes them).  The host reads back, every done_check passes, how many agents
         each step moved and the info counts, as _run_eposide_fused; updates behind a step that moved nobody are gated off on the
         device, and the counters follow."""
         from dqn_based_uav_3d_path_planer_amd.loop import DQNSlotsHotLoop
@@ -639,7 +641,7 @@ class PathPlan_City:
         if self._slots_hot is None:
             self._slots_hot = DQNSlotsHotLoop(ring, Ls, batch_now, seed=self.seed, eps=eps_rate, counter=self._slots_counter,
                                               learn_start=trs[0].Batch_Size + 1, auto_reset=False, skip_done=True, info=self._info,
-                                              gate_updates=True)
+                                              gate_updates=True, multi_update=Ls[0].n_actions + int(Ls[0].dueling) <= 4)
         hot = self._slots_hot
         hot.set_eps(eps_rate if train else 0.0)
         k = 1 if self.record_path else min(self.done_check, ring.frames - 2)

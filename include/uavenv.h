@@ -415,6 +415,28 @@ int uavenv_dqn_act(const UavDqnNet *net, const void *obs_dev, int32_t obs_dtype,
 #define UAVENV_DQN_MAX_SLOTS 8
 int uavenv_dqn_act_slots(const UavDqnNet *const *nets, int32_t n_nets, const void *obs_dev, int32_t obs_dtype, int32_t n_envs,
                          float eps, uint64_t seed, uint64_t counter, int32_t *index_out_dev, float *q_out_dev, void *stream);
+/* The learning half for one net per UAV slot: uavenv_dqn_grad for n_nets nets in ONE launch (grid rows x n_nets).  All slots read
+ * the one packed ring; slot j trains nets[j] (host array) on ITS batch (frame, agent) pairs pairs_dev[j][batch][2] -- explicit and
+ * mandatory, uavenv_replay_draw_slots' layout -- and writes partials[j] (host array of device pointers), each
+ * uavenv_dqn_partial_rows(batch) x uavenv_dqn_partial_stride(net) floats.  Row x of partials[j] is bit for bit the row that
+ * uavenv_dqn_grad(ring, head, filled, batch, seed, counter, pairs_dev + j * batch * 2, nets[j], kind, gamma, huber, partials[j])
+ * writes.  UAVENV_EINVAL, with nothing enqueued, for whatever uavenv_dqn_grad refuses of any slot and for: n_nets < 1 or
+ * > UAVENV_DQN_MAX_SLOTS; a ring that is not UAVENV_OBS_PACKED; an f16-MFMA net; more than 4 layer-2 outputs (n_actions + dueling);
+ * nets that differ in n_actions or dueling; pairs_dev NULL or off 8 bytes; a partials entry NULL or off 16 bytes; two slots sharing
+ * `local` or a partials buffer. */
+int uavenv_dqn_grad_slots(const UavReplayRing *ring, int32_t head, int32_t filled, int32_t batch, uint64_t seed, uint64_t counter,
+                          const int32_t *pairs_dev, const UavDqnNet *const *nets, int32_t n_nets, int32_t kind, float gamma,
+                          int32_t huber, float *const *partials, void *stream);
+/* uavenv_dqn_reduce_adam_gated for n_nets nets in ONE launch (grid (num_params + 2 + 31) / 32 x n_nets): slot j sums its
+ * n_partials rows of partials[j] and takes Adam step step_t[j] (host array, each > 0: the slots' update counts may differ) with
+ * the hard target copy where hard_update[j] != 0 (host array); loss_out (host array, nullable as a whole and per entry) holds
+ * the slots' device loss cells.  One gate for all slots.  Parameters, moments, target and loss of slot j are bit for bit those of
+ * uavenv_dqn_reduce_adam_gated(nets[j], partials[j], n_partials, ..., step_t[j], hard_update[j], loss_out[j], NULL, go_word_dev,
+ * go_value).  UAVENV_EINVAL, with nothing enqueued, for whatever that entry refuses of any slot, n_nets out of range, differing
+ * heads, a partials entry off 16 bytes, or two slots sharing `local` or a partials buffer. */
+int uavenv_dqn_reduce_adam_slots(const UavDqnNet *const *nets, int32_t n_nets, float *const *partials, int32_t n_partials, float lr,
+                                 float beta1, float beta2, float eps, const int32_t *step_t, const int32_t *hard_update,
+                                 float *const *loss_out, const uint32_t *go_word_dev, uint32_t go_value, void *stream);
 
 /* ---- greedy policy evaluation: whole episodes in one launch (Trainer/DuelingDQN_Trainer.py:90, Is_Train == 0) ----------------
  * Episode e (0 <= e < n) flies scenario row (first + e) mod m of a scenario set -- the env's bank (start_goal / sub / nsub NULL) or
@@ -908,6 +930,10 @@ typedef struct UavDqnSlotsLoop UavDqnSlotsLoop;
 int uavenv_dqn_slots_loop_create(const UavDqnSlotsLoopConfig *cfg, UavDqnSlotsLoop **out);
 int uavenv_dqn_slots_loop_destroy(UavDqnSlotsLoop *loop);
 int uavenv_dqn_slots_loop_set_eps(UavDqnSlotsLoop *loop, float eps);
+/* on != 0: from the next run the learning phase of a pass is ONE uavenv_dqn_grad_slots and ONE uavenv_dqn_reduce_adam_slots for all
+ * slots (a pass is 5 launches instead of 3 + 2 n_slots) -- same parameters, moments, losses and epochs, bit for bit.  Off by
+ * default.  UAVENV_EINVAL, with the loop left as it was, when the loop's nets have more than 4 layer-2 outputs. */
+int uavenv_dqn_slots_loop_set_multi_update(UavDqnSlotsLoop *loop, int32_t on);
 /* Enqueue n_steps passes on `stream`; never synchronises. */
 int uavenv_dqn_slots_loop_run(UavDqnSlotsLoop *loop, int32_t n_steps, void *stream);
 int uavenv_dqn_slots_loop_get(const UavDqnSlotsLoop *loop, UavDqnSlotsLoopCursor *out);

@@ -13,12 +13,19 @@ for bit.  Then both are warmed up and timed with device events around windows of
 one process; the median of `--windows` windows is reported with their spread (min .. max).
     python scripts/time_slots_loop.py [--passes 2000] [--windows 5] [--out profiles/dqn_slots_loop_times.json]
     python scripts/time_slots_loop.py --profile-run     (the C loop alone, for rocprofv3 --kernel-trace --stats in its own process)
+--multi-update times the C loop against itself: its learning phase slot by slot (U gradient and U Adam launches per pass) and as
+one gradient and one Adam launch for all slots (DQNSlotsHotLoop(multi_update=True): uavenv_dqn_grad_slots,
+uavenv_dqn_reduce_adam_slots), same shapes, same method, both forms first checked equal on a short run.  Each shape is measured
+by a child process of its own under a time limit; the first failure ends the run.
+    python scripts/time_slots_loop.py --multi-update [--out profiles/dqn_slots_update_times.json]
+    python scripts/time_slots_loop.py --multi-update --profile-run     (the multi-update loop alone, for rocprofv3)
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -126,9 +133,70 @@ def measure(n_envs, U, batch, ring_transitions, passes, windows, check_passes):
     return res
 
 
-def profile_run(passes):
+def measure_update(n_envs, U, batch, ring_transitions, passes, windows, check_passes):
+    """The C loop with per-slot updates against the C loop with multi_update, from the same start."""
+    env_a, ring_a, La = build(n_envs, U, ring_transitions)
+    env_b, ring_b, Lb = build(n_envs, U, ring_transitions)
+    per_slot = DQNSlotsHotLoop(ring_a, La, batch, seed=SEED, eps=EPS, auto_reset=True, skip_done=True)
+    multi = DQNSlotsHotLoop(ring_b, Lb, batch, seed=SEED, eps=EPS, auto_reset=True, skip_done=True, multi_update=True)
+    per_slot.run(check_passes)
+    multi.run(check_passes)
+    torch.cuda.synchronize()
+    equal = all(torch.equal(getattr(ring_a, k), getattr(ring_b, k)) for k in ("obs", "action", "reward", "done", "valid"))
+    equal = equal and all(torch.equal(a.flat, b.flat) and a.epoch == b.epoch and float(a.loss) == float(b.loss) for a, b in zip(La, Lb))
+    equal = equal and (ring_a.head, ring_a.filled) == (ring_b.head, ring_b.filled) and La[0].epoch > 0
+    if not equal:
+        raise SystemExit(f"U={U}: the per-slot and the multi-update loop differ after {check_passes} passes")
+    warm = max(50, passes // 10)
+    per_slot.run(warm)
+    multi.run(warm)
+    t_per, t_multi = [], []
+    for _ in range(windows):                          # the two forms alternate
+        t_multi.append(window(multi.run, passes))
+        t_per.append(window(per_slot.run, passes))
+    N = env_a.N
+    res = {"uav_per_env": U, "n_envs": n_envs, "agents": N, "batch_per_slot": batch, "ring_frames": ring_a.frames,
+           "ring_transitions": (ring_a.frames - 1) * N, "passes_per_window": passes, "windows": windows,
+           "equal_after_passes": check_passes, "launches_per_pass_per_slot": 3 + 2 * U, "launches_per_pass_multi_update": 5}
+    for name, t in (("per_slot", t_per), ("multi_update", t_multi)):
+        med = float(np.median(t))
+        res[name] = {"us_per_pass_windows": [round(x, 3) for x in t], "us_per_pass_median": round(med, 3),
+                     "us_per_pass_min": round(min(t), 3), "us_per_pass_max": round(max(t), 3),
+                     "agent_steps_per_s": round(N / med * 1e6), "updates_per_s": round(U / med * 1e6)}
+    res["speedup_median"] = round(res["per_slot"]["us_per_pass_median"] / res["multi_update"]["us_per_pass_median"], 3)
+    # the condition for switching a caller over: the multi form's slowest window beats the per-slot form's fastest
+    res["multi_update_faster_beyond_spread"] = bool(max(t_multi) < min(t_per))
+    res["device"] = torch.cuda.get_device_name(0)
+    per_slot.close()
+    multi.close()
+    env_a.close()
+    env_b.close()
+    return res
+
+
+ROWS = ((16384, 4), (32768, 2))                       # (envs, UAV slots): N = 65 536 agents
+
+
+def multi_update_rows(a):
+    """One child process per shape, each under its own time limit; the first failure ends the run."""
+    shapes = []
+    for n_envs, U in ROWS:
+        cmd = ["timeout", "-k", "10", str(a.row_timeout), sys.executable, os.path.abspath(__file__), "--multi-update", "--row",
+               str(n_envs), str(U), "--passes", str(a.passes), "--windows", str(a.windows), "--check-passes", str(a.check_passes)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            sys.stderr.write(r.stdout + r.stderr)
+            raise SystemExit(f"the shape {n_envs} x {U} ended with status {r.returncode}: nothing further is started")
+        shapes.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        print(json.dumps(shapes[-1]), flush=True)
+    return {"device": shapes[0]["device"], "method": "device events around windows of passes, both forms warmed up, alternating in one "
+            "process per shape, median of the windows; spread = min .. max of the windows", "shapes": shapes,
+            "multi_update_faster_beyond_spread_at_every_shape": all(x["multi_update_faster_beyond_spread"] for x in shapes)}
+
+
+def profile_run(passes, multi_update=False):
     env, ring, Ls = build(16384, 4, 1 << 20)
-    loop = DQNSlotsHotLoop(ring, Ls, 16384, seed=SEED, eps=EPS, auto_reset=True, skip_done=True)
+    loop = DQNSlotsHotLoop(ring, Ls, 16384, seed=SEED, eps=EPS, auto_reset=True, skip_done=True, multi_update=multi_update)
     loop.run(passes)
     torch.cuda.synchronize()
     loop.close()
@@ -140,12 +208,27 @@ def main():
     ap.add_argument("--passes", type=int, default=2000)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--check-passes", type=int, default=8)
-    ap.add_argument("--out", default=os.path.join("profiles", "dqn_slots_loop_times.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--profile-run", action="store_true")
+    ap.add_argument("--multi-update", action="store_true")
+    ap.add_argument("--row", type=int, nargs=2, metavar=("ENVS", "SLOTS"), help="(--multi-update's children) measure this shape only")
+    ap.add_argument("--row-timeout", type=int, default=420, help="seconds a --multi-update shape may take")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join("profiles", "dqn_slots_update_times.json" if a.multi_update else "dqn_slots_loop_times.json")
+    if a.multi_update and not a.profile_run and a.row is None:     # (the parent never opens the device)
+        out = multi_update_rows(a)
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        return
     assert torch.cuda.is_available(), "needs an MI355X"
     if a.profile_run:
-        profile_run(min(a.passes, 500))
+        profile_run(min(a.passes, 500), multi_update=a.multi_update)
+        return
+    if a.row is not None:
+        print(json.dumps(measure_update(a.row[0], a.row[1], 16384, 1 << 20, a.passes, a.windows, a.check_passes)))
         return
     out = {"device": torch.cuda.get_device_name(0), "method": "device events around windows of passes, both forms warmed up, "
            "alternating in one process, median of the windows; spread = min .. max of the windows",
