@@ -91,10 +91,11 @@ __global__ void k_replay_draw(int frames, int n_agents, int head, int batch, Rep
 
 // The draws over VALID rows only.  The reference's buffers never hold a row of a finished agent (run_eposide stops pushing for it,
 // Envs/PathPlan_City.py:456-459; BaseClass/replay_buffer.py:41-51 samples what was pushed); the ring keeps such rows with valid = 0.
-// Draw s of slot j (s in [j * batch, (j + 1) * batch)) looks at permutation positions s, s + S, s + 2 S, ... (S = n_slots * batch,
-// positions < D) until the row (frame, env, first_slot + j) is valid: rejection sampling over a bijection, so accepted rows are
-// uniform over the valid ones and stay distinct within a slot.  A draw that runs out of tries keeps its first row (valid = 0: weight
-// 0 in the update, the behaviour before this kernel).
+// Draw s of slot j (s in [j * batch, (j + 1) * batch)) looks at permutation positions s0, s0 + S, s0 + 2 S, ... (s0 = s mod D,
+// S = n_slots * batch, positions < D) until the row (frame, env, first_slot + j) is valid: rejection sampling over a bijection, so
+// accepted rows are uniform over the valid ones and stay distinct within a slot (while batch <= D).  A draw that runs out of tries
+// keeps its first row (valid = 0: weight 0 in the update, the behaviour before this kernel).  s0 = s mod D is k_replay_draw's wrap:
+// with S > D (a loop that starts learning at `batch` stored rows while it draws for every slot) try 0 always names a stored row.
 __global__ void k_replay_draw_valid(int frames, int n_envs, int head, int batch, int n_slots, int uav, int first_slot,
                                     const unsigned char *__restrict__ valid, int max_tries, ReplayPerm perm, int32_t *__restrict__ out)
 {
@@ -103,8 +104,9 @@ __global__ void k_replay_draw_valid(int frames, int n_envs, int head, int batch,
         const int slot = first_slot + s / batch;
         int f0 = 0, e0 = 0;
         bool found = false;
+        const uint32_t s0 = (uint32_t)s < perm.D ? (uint32_t)s : (uint32_t)s % perm.D;
         for (int t = 0; t < max_tries && !found; ++t) {
-            const uint64_t q = (uint64_t)s + (uint64_t)t * (uint64_t)total;
+            const uint64_t q = (uint64_t)s0 + (uint64_t)t * (uint64_t)total;
             if (q >= (uint64_t)perm.D) break;
             int f, e;
             replay_slot_to_frame(perm, replay_perm_apply(perm, (uint32_t)q), head, frames, f, e);
@@ -128,8 +130,9 @@ __global__ void k_replay_draw_slots(int frames, int n_envs, int head, int batch,
         int f0 = 0, e0 = 0;
         if (valid) {
             bool found = false;
+            const uint32_t s0 = (uint32_t)s < perm.D ? (uint32_t)s : (uint32_t)s % perm.D;
             for (int t = 0; t < max_tries && !found; ++t) {
-                const uint64_t q = (uint64_t)s + (uint64_t)t * (uint64_t)total;
+                const uint64_t q = (uint64_t)s0 + (uint64_t)t * (uint64_t)total;
                 if (q >= (uint64_t)perm.D) break;
                 int f, e;
                 replay_slot_to_frame(perm, replay_perm_apply(perm, (uint32_t)q), head, frames, f, e);

@@ -260,11 +260,12 @@ int uavenv_replay_draw(int32_t frames, int32_t n_agents, int32_t head, int32_t f
 /* The same draws over VALID rows only -- the reference's buffers never hold a row of a finished agent (run_eposide stops pushing
  * for it, Envs/PathPlan_City.py:456-459; BaseClass/replay_buffer.py:41-51), the ring keeps such rows with valid = 0.  (frame, env)
  * pairs for n_slots UAV slots at once: slot first_slot + j takes draws [j * batch, (j + 1) * batch) and tests ITS row
- * valid_dev[(frame * n_envs + env) * uav_per_env + slot] (the ring's valid plane).  Draw s looks at permutation positions s,
- * s + S, s + 2 S, ... (S = n_slots * batch; positions below filled * n_envs; at most max_tries of them) and takes the first
- * valid row: rejection sampling over a bijection -- uniform over the valid rows, distinct within a slot.  With every row valid
- * the result equals uavenv_replay_draw(batch * n_slots).  A draw that finds no valid row keeps its first one (weight 0 in the
- * update through the valid plane). */
+ * valid_dev[(frame * n_envs + env) * uav_per_env + slot] (the ring's valid plane).  Try t of draw s looks at permutation position
+ * (s mod D) + t S (D = filled * n_envs stored rows, S = n_slots * batch) while that is below D and t < max_tries, and the draw
+ * takes the first valid row: rejection sampling over a bijection -- uniform over the valid rows, distinct within a slot while
+ * batch <= D.  With every row valid the result equals uavenv_replay_draw(batch * n_slots) for every S and D: S > D wraps as
+ * it does there (s mod D), so every pair names a stored row.  A draw that finds no valid row keeps the row of its try 0 (weight
+ * 0 in the update through the valid plane). */
 #define UAVENV_DRAW_MAX_TRIES 8
 int uavenv_replay_draw_valid(int32_t frames, int32_t n_envs, int32_t head, int32_t filled, int32_t batch, int32_t n_slots,
                              int32_t uav_per_env, int32_t first_slot, const uint8_t *valid_dev, int32_t max_tries, uint64_t seed,

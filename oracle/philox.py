@@ -8,6 +8,8 @@
   DISTINCT transitions; the device realises that as the first `batch` images of a keyed pseudo-random permutation
   of the D = filled * n_agents stored transitions (6-round alternating Feistel network over ceil(log2 D) bits,
   cycle-walked into [0, D); csrc/uavenv_device.hpp: replay_perm / replay_perm_apply).
+* replay_draws_valid / replay_draws_slots: the same draws over the valid rows only and as one (frame, agent) list for every UAV slot
+  (uavenv_replay_draw_valid / uavenv_replay_draw_slots, csrc/replay.hip); draw s starts at permutation position s mod D.
 * act_draws: the epsilon-greedy stream of uavenv_dqn_act / uavenv_select_actions (DuelingDQN_Trainer.py:86-97).
 * the other seven device streams ("Random streams"), written from include/uavenv.h, DESIGN.md and the kernels' comments:
   randn (uavenv_randn: every rsample() of SAC training), eval_noise (evaluate.sac_noise / the SAC evaluation's sample mode),
@@ -59,57 +61,89 @@ def fmix32(h):
     return h
 
 
-def replay_slots(batch: int, seed: int, counter: int, filled: int, n_agents: int) -> np.ndarray:
-    """Transition slot (0 = newest frame's agent 0 ... D-1) of samples 0..batch-1."""
+def replay_slots(batch: int, seed: int, counter, filled: int, n_agents: int, *, positions=None, swap_halves: bool = False,
+                 rounds: int = 6, walk: bool = True) -> np.ndarray:
+    """Transition slot (0 = newest frame's agent 0 ... D-1) of samples 0..batch-1 -- or of the permutation positions `positions`
+    (any non-negative integers; taken mod D), and then `counter` may be an array of their shape: position i under the keys of
+    update counter[i].  swap_halves / rounds / walk exist for the mutation tests only."""
     D = filled * n_agents
+    pos = np.arange(batch, dtype=np.uint64) if positions is None else np.asarray(positions, dtype=np.uint64)
     if D <= 1:
-        return np.zeros(batch, dtype=np.int64)
-    lo_c, hi_c = counter & 0xFFFFFFFF, (counter >> 32) & 0xFFFFFFFF
-    a = philox4x32_10(np.array([0, lo_c, hi_c, 0x5A3B]), _key(seed))
-    b = philox4x32_10(np.array([1, lo_c, hi_c, 0x5A3B]), _key(seed))
-    keys = [np.uint64(v) for v in (a[0], a[1], a[2], a[3], b[0], b[1])]
+        return np.zeros(pos.shape, dtype=np.int64)
+    per_position = np.ndim(counter) > 0
+    c = np.asarray(counter, dtype=np.uint64) if per_position else np.uint64(int(counter) & 0xFFFFFFFFFFFFFFFF)
+    lo_c, hi_c = c & U32, c >> np.uint64(32)
+    a = philox4x32_10(_words(0, lo_c, hi_c, 0x5A3B), _key(seed))
+    b = philox4x32_10(_words(1, lo_c, hi_c, 0x5A3B), _key(seed))
+    keys = [k.astype(np.uint64) for k in (a[..., 0], a[..., 1], a[..., 2], a[..., 3], b[..., 0], b[..., 1])]
     bits = max(2, int(D - 1).bit_length())
     la = bits // 2
     lb = bits - la
-    ma, mb = np.uint64((1 << la) - 1), np.uint64((1 << lb) - 1)
+    if swap_halves:
+        la, lb = lb, la
+    ma = np.uint64((1 << la) - 1)
     sa, sb = np.uint64(32 - la), np.uint64(32 - lb)
-    x = (np.arange(batch, dtype=np.uint64) % np.uint64(D))
-    todo = np.ones(batch, dtype=bool)
+    x = pos % np.uint64(D)
+    todo = np.ones(x.shape, dtype=bool)
     while todo.any():
         v = x[todo]
+        k = [kr[todo] for kr in keys] if per_position else keys
         lo, hi = v & ma, v >> np.uint64(la)
-        for r in range(0, 6, 2):
-            lo = lo ^ (fmix32(hi ^ keys[r]) >> sa)             # even round: low part ^= F(high part)
-            hi = hi ^ (fmix32(lo ^ keys[r + 1]) >> sb)         # odd round: high part ^= F(low part)
+        for r in range(rounds):
+            if r % 2 == 0:
+                lo = lo ^ (fmix32(hi ^ k[r]) >> sa)                # even round: low part ^= F(high part)
+            else:
+                hi = hi ^ (fmix32(lo ^ k[r]) >> sb)                # odd round: high part ^= F(low part)
         v = (hi << np.uint64(la)) | lo
+        if not walk:
+            x[todo] = v % np.uint64(D)
+            break
         x[todo] = v
         todo[todo] = v >= np.uint64(D)
     return x.astype(np.int64)
 
 
-def replay_draws(batch: int, seed: int, counter: int, head: int, filled: int, frames: int, n_agents: int):
-    """-> (frame [batch], agent [batch]) of the transitions update (seed, counter) must use."""
-    slot = replay_slots(batch, seed, counter, filled, n_agents)
-    back = slot // n_agents
+def slots_to_rows(slot, head: int, frames: int, n_agents: int, *, short_division: bool = False, head_offset: int = 1):
+    """Transition slot -> (frame, agent): slot // n_agents + 1 frames behind the ring head.  short_division (the quotient as
+    floor(slot * floor(2^32 / n_agents) / 2^32) -- at most one short -- WITHOUT the correction) and head_offset exist for the
+    mutation tests only."""
+    slot = np.asarray(slot, dtype=np.int64)
+    if short_division:
+        magic = min((1 << 32) // n_agents, 0xFFFFFFFF)
+        back = ((slot.astype(np.uint64) * np.uint64(magic)) >> np.uint64(32)).astype(np.int64)    # slot, magic < 2^32: fits
+    else:
+        back = slot // n_agents
     agent = slot - back * n_agents
-    f = (head - 1 - back) % frames
+    f = (head - head_offset - back) % frames
     return f.astype(np.int64), agent.astype(np.int64)
 
 
+def replay_draws(batch: int, seed: int, counter: int, head: int, filled: int, frames: int, n_agents: int, **mutation):
+    """-> (frame [batch], agent [batch]) of the transitions update (seed, counter) must use.  Sample s >= D = filled * n_agents
+    wraps to sample s mod D (the reference raises there).  **mutation: replay_slots' / slots_to_rows' mutation knobs."""
+    to_rows = {k: mutation.pop(k) for k in ("short_division", "head_offset") if k in mutation}
+    slot = replay_slots(batch, seed, counter, filled, n_agents, **mutation)
+    return slots_to_rows(slot, head, frames, n_agents, **to_rows)
+
+
 def replay_draws_valid(batch: int, n_slots: int, uav_per_env: int, first_slot: int, valid: np.ndarray, max_tries: int, seed: int,
-                       counter: int, head: int, filled: int, frames: int, n_envs: int):
-    """uavenv_replay_draw_valid: -> (frame [n_slots * batch], env [n_slots * batch], found [n_slots * batch]).  valid: the ring's
-    plane [frames][n_envs * uav_per_env].  Draw s of slot first_slot + s // batch walks permutation positions s, s + S, s + 2 S,
-    ... (S = n_slots * batch, positions < filled * n_envs, at most max_tries) to the first row of ITS slot with valid != 0; a draw
-    that finds none keeps its first row."""
+                       counter: int, head: int, filled: int, frames: int, n_envs: int, *, stride=None):
+    """uavenv_replay_draw_valid: -> (frame [S], env [S], found [S]), S = n_slots * batch.  valid: the ring's plane
+    [frames][n_envs * uav_per_env].  Try t of draw s (slot first_slot + s // batch) looks at permutation position
+    (s mod D) + t S while that is < D = filled * n_envs and t < max_tries, and stops at the first row of ITS slot with valid != 0; a
+    draw that finds none keeps the row of its try 0.  S > D is defined by the `mod`: with every row valid the result is
+    replay_draws(S) for every S and D, and every output is a stored row.  stride (the try stride, S) exists for the mutation tests
+    only."""
     S, D = batch * n_slots, filled * n_envs
-    n_pos = min(D, S * max_tries)
+    stride = S if stride is None else stride
+    first = np.arange(S, dtype=np.int64) % D
+    n_pos = min(D, int(first.max()) + 1 + stride * (max_tries - 1))
     f_all, e_all = replay_draws(n_pos, seed, counter, head, filled, frames, n_envs)
     valid = np.asarray(valid).reshape(frames, n_envs, uav_per_env)
-    f_out, e_out, found = f_all[:S].copy(), e_all[:S].copy(), np.zeros(S, dtype=bool)
+    f_out, e_out, found = f_all[first].copy(), e_all[first].copy(), np.zeros(S, dtype=bool)
     slot = first_slot + np.arange(S) // batch
     for t in range(max_tries):
-        q = np.arange(S) + t * S
+        q = first + t * stride
         ok = (q < D) & ~found
         if not ok.any():
             break
@@ -118,6 +152,22 @@ def replay_draws_valid(batch: int, n_slots: int, uav_per_env: int, first_slot: i
         idx = np.nonzero(ok)[0][hit]
         f_out[idx], e_out[idx], found[idx] = f_all[qq[hit]], e_all[qq[hit]], True
     return f_out, e_out, found
+
+
+def replay_draws_slots(batch: int, uav_per_env: int, valid, max_tries: int, seed: int, counter: int, head: int, filled: int,
+                       frames: int, n_envs: int):
+    """uavenv_replay_draw_slots: -> (frame [U * batch], agent [U * batch], found [U * batch]) with agent = env * U + slot and slot =
+    s // batch (U = uav_per_env): the draws of replay_draws_valid(batch, U, U, 0, valid, ...) with a plane, of
+    replay_draws(U * batch) over the n_envs-wide ring with valid None (found is all True then: no row is tested)."""
+    S = batch * uav_per_env
+    slot = np.arange(S, dtype=np.int64) // batch
+    if valid is None:
+        f, e = replay_draws(S, seed, counter, head, filled, frames, n_envs)
+        found = np.ones(S, dtype=bool)
+    else:
+        f, e, found = replay_draws_valid(batch, uav_per_env, uav_per_env, 0, valid, max_tries, seed, counter, head, filled, frames,
+                                         n_envs)
+    return f, e * uav_per_env + slot, found
 
 
 def act_draws(n: int, seed: int, counter: int, n_actions: int):

@@ -226,7 +226,7 @@ def test_draw_slots_equals_the_existing_draws(U, n_envs, batch, frames, head, fi
                   counter)
         got = run(lib.uavenv_replay_draw_slots, frames, n_envs, head, filled, batch, U, v.data_ptr(), L.DRAW_MAX_TRIES, seed, counter)
         assert np.array_equal(got[:, 0], ref[:, 0]) and np.array_equal(got[:, 1], ref[:, 1] * U + slot), k
-        if k == 0 and filled * n_envs >= total:              # (a draw past the stored rows: the valid form keeps (0, 0), the other wraps)
+        if k == 0:                                             # (a draw past the stored rows wraps in both forms: draw s mod D)
             all_rows = run(lib.uavenv_replay_draw_slots, frames, n_envs, head, filled, batch, U, None, L.DRAW_MAX_TRIES, seed, counter)
             assert np.array_equal(got, all_rows)
         if k == 1 and filled * n_envs >= 8 * total:            # enough tries: (almost) every draw found a valid row

@@ -80,6 +80,115 @@ def test_valid_only_draws_reject_over_the_permutation():
     assert (f2 == fs).all() and (e2 == es).all()                       # no second position exists: every draw keeps its first row
 
 
+def _planes(rng, frames, n_envs, U):
+    """All rows valid; 60 % valid; one slot (the last) without a single valid row."""
+    dead = (rng.random((frames, n_envs, U)) < 0.9).astype(np.uint8)
+    dead[:, :, U - 1] = 0
+    return [np.ones((frames, n_envs, U), dtype=np.uint8), (rng.random((frames, n_envs, U)) < 0.6).astype(np.uint8), dead]
+
+
+def _valid_draws_one_by_one(batch, n_slots, U, first_slot, valid, max_tries, seed, counter, head, filled, frames, n_envs):
+    """The rule of replay_draws_valid as a loop over draws and tries: try t of draw s looks at (s mod D) + t S while that is < D."""
+    S, D = batch * n_slots, filled * n_envs
+    fp, ep = px.replay_draws(D, seed, counter, head, filled, frames, n_envs)            # the whole permutation
+    valid = np.asarray(valid).reshape(frames, n_envs, U)
+    out = []
+    for s in range(S):
+        slot, row, hit = first_slot + s // batch, None, False
+        for t in range(max_tries):
+            p = s % D + t * S
+            if p >= D:
+                break
+            if t == 0:
+                row = (fp[p], ep[p])
+            if valid[fp[p], ep[p], slot]:
+                row, hit = (fp[p], ep[p]), True
+                break
+        out.append((row[0], row[1], hit))
+    o = np.array(out, dtype=np.int64)
+    return o[:, 0], o[:, 1], o[:, 2].astype(bool)
+
+
+def test_valid_only_draws_with_more_draws_than_stored_rows():
+    """S = n_slots * batch draws over D = filled * n_envs stored rows, D far below, just below, at, just above and far above S (the
+    slots loop learns from `batch` stored rows on while it draws for every slot: 4 envs x 4 slots x batch 64 start at D = 68 <
+    S = 256).  Every output has length S and names a stored row; with every row valid the result is replay_draws(S), wrap
+    included; rows are distinct within a slot whenever batch <= D; found is true exactly where the returned row is valid."""
+    batch, n_envs = 64, 4
+    rng = np.random.default_rng(11)
+    for U, n_slots, first_slot in ((4, 4, 0), (2, 2, 0), (1, 1, 0), (4, 2, 1)):
+        S = batch * n_slots
+        fills = sorted({1, 3, 16, 17, (S - 1) // n_envs, S // n_envs, S // n_envs + 1, 8 * S // n_envs})
+        for filled in fills:
+            D = filled * n_envs
+            frames = filled + 1 + filled % 3
+            head = (5 * filled) % frames
+            for max_tries in (1, 8):
+                for k, plane in enumerate(_planes(rng, frames, n_envs, U)):
+                    args = (batch, n_slots, U, first_slot, plane, max_tries, 0x5EED00000007, (3 << 32) + filled, head, filled, frames, n_envs)
+                    f, e, found = px.replay_draws_valid(*args)
+                    assert f.shape == e.shape == found.shape == (S,)
+                    f1, e1, found1 = _valid_draws_one_by_one(*args)
+                    assert np.array_equal(f, f1) and np.array_equal(e, e1) and np.array_equal(found, found1)
+                    back = (head - 1 - f) % frames
+                    assert back.min() >= 0 and back.max() < filled and e.min() >= 0 and e.max() < n_envs      # a stored row
+                    slot = first_slot + np.arange(S) // batch
+                    assert np.array_equal(found, plane[f, e, slot] != 0)
+                    f0, e0 = px.replay_draws(S, args[6], args[7], head, filled, frames, n_envs)
+                    assert np.array_equal(f[~found], f0[~found]) and np.array_equal(e[~found], e0[~found])   # try 0's row kept
+                    if k == 0:
+                        assert found.all() and np.array_equal(f, f0) and np.array_equal(e, e0)
+                    if k == 2 and first_slot + n_slots == U:
+                        assert not found[slot == U - 1].any()
+                    if batch <= D:
+                        for j in range(n_slots):
+                            m = (slot == first_slot + j) & found
+                            assert len(np.unique(back[m] * n_envs + e[m])) == m.sum()
+                    if S <= D:                                            # nothing wraps: S distinct first positions
+                        assert len(np.unique((head - 1 - f0) % frames * n_envs + e0)) == S
+
+
+def test_draws_for_every_slot_as_frame_agent_pairs():
+    """replay_draws_slots restates uavenv_replay_draw_slots: (frame, env * U + slot); with a plane the rows of replay_draws_valid for
+    all U slots, without one those of replay_draws(U * batch) -- the two agree when every row is valid, for S below and above D."""
+    batch, n_envs, U = 64, 4, 4
+    S = batch * U
+    slot = np.arange(S) // batch
+    rng = np.random.default_rng(12)
+    for filled in (1, 17, 63, 64, 65, 600):
+        frames, head = filled + 2, filled // 2
+        f0, e0 = px.replay_draws(S, 21, 1 << 33, head, filled, frames, n_envs)
+        fa, aa, fo = px.replay_draws_slots(batch, U, None, 8, 21, 1 << 33, head, filled, frames, n_envs)
+        assert fo.all() and np.array_equal(fa, f0) and np.array_equal(aa, e0 * U + slot)
+        for k, plane in enumerate(_planes(rng, frames, n_envs, U)):
+            fv, ev, found = px.replay_draws_valid(batch, U, U, 0, plane, 8, 21, 1 << 33, head, filled, frames, n_envs)
+            fs, as_, fos = px.replay_draws_slots(batch, U, plane, 8, 21, 1 << 33, head, filled, frames, n_envs)
+            assert np.array_equal(fs, fv) and np.array_equal(as_, ev * U + slot) and np.array_equal(fos, found)
+            assert as_.min() >= 0 and as_.max() < n_envs * U and np.array_equal(as_ % U, slot)
+            assert np.array_equal(fos, plane.reshape(frames, n_envs * U)[fs, as_] != 0)
+            if k == 0:
+                assert np.array_equal(fs, fa) and np.array_equal(as_, aa)
+
+
+def test_first_draw_is_uniform_on_tiny_rings():
+    """The slot of draw 0 over 4 000 updates (counters (5 << 32) + k at one seed) of rings with D = 2 ... 33 stored rows, the sizes
+    where the Feistel halves are one to three bits wide and the cycle-walk rejects up to half of its passes: every cell within
+    4.5 sigma of N / D (binomial; the largest seen is 2.9 sigma).  The GPU tests assert equality with this oracle, so the law is
+    tested here alone.  PAIRS of draws are not uniform on such rings -- at D = 5 (3 bits, la = 1) the ordered pair (draw 0, draw 1)
+    is 7.9 sigma off: six rounds over 3 bits are not a uniform random permutation ("Random streams") -- and are not
+    asserted."""
+    N, seed = 4000, 0x1234567890
+    for D in (2, 3, 5, 9, 17, 33):
+        counters = (5 << 32) + np.arange(N, dtype=np.uint64)
+        first = px.replay_slots(N, seed, counters, D, 1, positions=np.zeros(N, dtype=np.uint64))      # draw 0 of each update
+        for k in range(0, N, 397):
+            assert first[k] == px.replay_slots(1, seed, (5 << 32) + k, D, 1)[0]
+        hits = np.bincount(first, minlength=D)
+        assert hits.sum() == N and len(hits) == D
+        sigma = np.sqrt(N * (1.0 / D) * (1.0 - 1.0 / D))
+        assert np.abs(hits - N / D).max() <= 4.5 * sigma, (D, hits)
+
+
 def test_u53_range_and_monotonicity():
     assert px.u53(0, 0) == 0.0
     assert px.u53(2 ** 32 - 1, 2 ** 32 - 1) == 1.0 - 2.0 ** -53
