@@ -257,17 +257,18 @@ __device__ __forceinline__ void td_backward(const GradArgs &g, const float *W2l,
     dq *= p_w;                                        // (x 1 without prioritised replay: bit-identical)
     if (g.abs_td && gq == 0) g.abs_td[smp] = fabsf(delta);
     float dv[NMAX + 2];
-    const float inv_a = 1.0f / (float)g.n_actions;
+    if (g.dueling) {                                  // Q = V + A - mean(A)   (one wave-uniform decision around the unrolled loop, and
+        const float inv_a = 1.0f / (float)g.n_actions;    // the division -- ten dependent instructions -- only where it is used)
 #pragma unroll
-    for (int a = 0; a < NMAX; ++a) {
-        float d = 0.0f;
-        if (g.dueling) {                              // Q = V + A - mean(A)
+        for (int a = 0; a < NMAX; ++a) {
+            float d = 0.0f;
             if (a < g.n_actions) d = dq * ((a == p_act ? 1.0f : 0.0f) - inv_a);
             else if (a == g.n_actions) d = dq;
-        } else if (a == p_act) {
-            d = dq;
+            dv[a] = d;
         }
-        dv[a] = d;
+    } else {
+#pragma unroll
+        for (int a = 0; a < NMAX; ++a) dv[a] = a == p_act ? dq : 0.0f;
     }
     dv[NMAX] = per * p_valid * p_w;                   // loss and valid count ride along as two more columns
     dv[NMAX + 1] = p_valid;
@@ -280,18 +281,26 @@ __device__ __forceinline__ void td_backward(const GradArgs &g, const float *W2l,
     }
     // ---- dL/dH = relu'(h) * W2^T dout, and the forward H, into LDS for the weight-gradient products
     wave_lds_sync();
+    // (the layer-2 row outermost: `a < n2` is then ONE wave-uniform branch per row around sixteen FMAs; inside the loop over t it came
+    // out as a select behind every FMA.  Every dh element still sums its rows in the order a = 0, 1, ...)
+    floatx4 dh4[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        floatx4 dh = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int t = 0; t < 4; ++t) dh4[t] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-        for (int a = 0; a < NMAX; ++a) {
-            if (a < n2) {
+    for (int a = 0; a < NMAX; ++a) {
+        if (a < n2) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
                 const floatx4 wv4 = kKeepW2 ? Fl.w[a][t]
                                             : *reinterpret_cast<const floatx4 *>(W2l + a * kHid + 16 * t + 4 * gq);
-                dh[0] = fmaf(dv[a], wv4[0], dh[0]); dh[1] = fmaf(dv[a], wv4[1], dh[1]);
-                dh[2] = fmaf(dv[a], wv4[2], dh[2]); dh[3] = fmaf(dv[a], wv4[3], dh[3]);
+                dh4[t][0] = fmaf(dv[a], wv4[0], dh4[t][0]); dh4[t][1] = fmaf(dv[a], wv4[1], dh4[t][1]);
+                dh4[t][2] = fmaf(dv[a], wv4[2], dh4[t][2]); dh4[t][3] = fmaf(dv[a], wv4[3], dh4[t][3]);
             }
         }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        floatx4 dh = dh4[t];
         floatx4 hh;
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
@@ -739,13 +748,13 @@ struct GradAcc8 {
 
 // group 1's A operands of the six flag tiles, built ahead of the products (grad_products_split8)
 struct FlagOps {
-    half8 one[2][6];                 // (the 2^-11 operand of the mid term is derived from it behind the barrier: two instructions per dword)
+    half8 one[2][6];                 // (the 2^-11 operand of the mid term is derived from it behind the barrier: one instruction per dword)
 };
 __device__ __forceinline__ half8 tiny_of(const half8 &one)
 {
     uintx4 d = *reinterpret_cast<const uintx4 *>(&one);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) d[k] = (d[k] << 2) & 0x10001000u;          // 0x3c00 (1.0) -> 0x1000 (2^-11), per half
+    for (int k = 0; k < 4; ++k) d[k] &= 0x10001000u;                       // 0x3c00 (1.0) -> 0x1000 (2^-11), per half: bit 12 is set in both
     return *reinterpret_cast<const half8 *>(&d);
 }
 __device__ __forceinline__ void flag_ops_build(const GradLdsP &L, int r, int gq, FlagOps &F)
@@ -812,7 +821,8 @@ __device__ __forceinline__ void grad_products_split8(const GradLdsP &L, const fl
             for (int k = 0; k < 4; ++k) A.acc[u][k] += ch[u][k] * down;
         return;
     }
-    // group 0: the gathered scalar tile (entry r: packed dword 4 + r, 15 = the ones column) x dH, and H x dout (dW2^T)
+    // group 0: the gathered scalar tile (entry r: packed dword 4 + r, 15 = the ones column: dword 19, which grad_tile_packed8 stores as
+    // 1.0 -- a select per MFMA operand otherwise) x dH, and H x dout (dW2^T)
     const uint32_t *pr = L.Ps + 4 * gq * kPackedDwords;
     const int dsc = r < 15 ? 4 + r : 19;
     const float *ha = L.Hs + 4 * gq * kLh + 16 * strip + r;
@@ -829,12 +839,11 @@ __device__ __forceinline__ void grad_products_split8(const GradLdsP &L, const fl
             bo[q][i] = ob[s1 * kMaxOut];
         }
     floatx4 csc = floatx4{0.0f, 0.0f, 0.0f, 0.0f}, cw2 = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-    const bool ones = r == 15;
 #pragma unroll
     for (int q = 0; q < 2; ++q)
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            csc = mfma16(ones ? 1.0f : xs[q][i], dh[q][i], csc);
+            csc = mfma16(xs[q][i], dh[q][i], csc);
             cw2 = mfma16(hh[q][i], bo[q][i], cw2);
         }
 #pragma unroll
@@ -902,9 +911,11 @@ __device__ __forceinline__ void grad_tile_packed8(const GradArgs &g, const GradL
         }
         L_STAMP(7);                           // (diagnostics: layer 1 committed -- its loads have arrived; GLDS: still in flight)
         float *W2 = grp == 0 ? L.W2l : L.W2t, *b2 = grp == 0 ? L.b2l : L.b2t;
+        // (unguarded: the block holds kMaxOut rows = 4 x 256 floats; rows >= n2 get element 0's value and are never read -- every
+        // reader of W2l / W2t stops at n2 -- and four guarded stores were four exec-mask round trips ahead of the barrier)
+        static_assert(kMaxOut * kHid == 4 * 256, "the 256 threads of a group cover a whole fc2 block in four stores");
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (t256 + 256 * k < n2 * kHid) W2[t256 + 256 * k] = pw[k];
+        for (int k = 0; k < 4; ++k) W2[t256 + 256 * k] = pw[k];
         if (t256 < n2) b2[t256] = pb2;
         __syncthreads();                      // both weight sets staged
     }
@@ -917,7 +928,7 @@ __device__ __forceinline__ void grad_tile_packed8(const GradArgs &g, const GradL
         fwd_strip_split<false>(w1split_at(L.W1l), R, hl);
         w2_load<NMAX>(Fl, L.W2l, L.b2l, n2);
         q_strip<NMAX>(hl, Fl, n2, g.n_actions, g.dueling, ql);
-        if (gq == 0) prow_store_lds(L.Ps + (strip * 16 + r) * kPackedDwords, R);    // the s rows, for the dW1 product
+        if (gq == 0) prow_store_lds(L.Ps + (strip * 16 + r) * kPackedDwords, R, 0x3f800000u);    // the s rows, for the dW1 product; dword 19 = 1.0: its ones column
     } else {
         // ---- the bootstrap value of the TD target from s'
         int best = 0;
@@ -1018,8 +1029,10 @@ __global__ void __launch_bounds__(512) k_dqn_grad_packed8(Grad2Args ga)
         for (int u = 1; u < 5; ++u) UAV_ROW_ST4(out + j * kW + 16 * u + 4 * gq, A.acc[u]);
         float *t5 = out + j * kW + 80 + 4 * gq;
         if (gq == 0 || gq == 3) UAV_ROW_ST4(t5, A.acc[5]);
-        else if (gq == 1) { t5[0] = A.acc[5][0]; t5[1] = A.acc[5][1]; }
-        else { t5[2] = A.acc[5][2]; t5[3] = A.acc[5][3]; }
+        else {                                                       // columns 84, 85 (gq 1) / 90, 91 (gq 2): one 8-byte store of the chosen half
+            const int h = 2 * (gq - 1);
+            *reinterpret_cast<float2 *>(t5 + h) = gq == 1 ? make_float2(A.acc[5][0], A.acc[5][1]) : make_float2(A.acc[5][2], A.acc[5][3]);
+        }
     } else {
         const floatx4 sc = A.acc[0];
         if (gq < 2) UAV_ROW_ST4(out + j * kW + 4 * gq, sc);                                            // columns 0..7
@@ -1035,9 +1048,9 @@ __global__ void __launch_bounds__(512) k_dqn_grad_packed8(Grad2Args ga)
     __syncthreads();
     if (tid < NMAX + 2) {
         const float s = (L.red[tid] + L.red[(kMaxOut + 2) + tid]) + (L.red[2 * (kMaxOut + 2) + tid] + L.red[3 * (kMaxOut + 2) + tid]);
-        if (tid < n2) out[ob2 + tid] = s;
-        else if (tid == NMAX) out[g.P] = s;
-        else if (tid == NMAX + 1) out[g.P + 1] = s;
+        // db2 | loss sum, valid count: one store at a chosen address (columns n2 .. NMAX - 1 of the sums belong to no output)
+        float *dst = out + (tid < NMAX ? ob2 + tid : g.P + (tid - NMAX));
+        if (tid < n2 || tid >= NMAX) *dst = s;
     }
 }
 
@@ -1117,8 +1130,10 @@ __global__ void __launch_bounds__(512) k_dqn_grad_slots(GradSlotsArgs sa)
         for (int u = 1; u < 5; ++u) UAV_ROW_ST4(out + j * kW + 16 * u + 4 * gq, A.acc[u]);
         float *t5 = out + j * kW + 80 + 4 * gq;
         if (gq == 0 || gq == 3) UAV_ROW_ST4(t5, A.acc[5]);
-        else if (gq == 1) { t5[0] = A.acc[5][0]; t5[1] = A.acc[5][1]; }
-        else { t5[2] = A.acc[5][2]; t5[3] = A.acc[5][3]; }
+        else {                                                       // columns 84, 85 (gq 1) / 90, 91 (gq 2): one 8-byte store of the chosen half
+            const int h = 2 * (gq - 1);
+            *reinterpret_cast<float2 *>(t5 + h) = gq == 1 ? make_float2(A.acc[5][0], A.acc[5][1]) : make_float2(A.acc[5][2], A.acc[5][3]);
+        }
     } else {
         const floatx4 sc = A.acc[0];
         if (gq < 2) UAV_ROW_ST4(out + j * kW + 4 * gq, sc);                                            // columns 0..7
@@ -1134,9 +1149,9 @@ __global__ void __launch_bounds__(512) k_dqn_grad_slots(GradSlotsArgs sa)
     __syncthreads();
     if (tid < NMAX + 2) {
         const float s = (L.red[tid] + L.red[(kMaxOut + 2) + tid]) + (L.red[2 * (kMaxOut + 2) + tid] + L.red[3 * (kMaxOut + 2) + tid]);
-        if (tid < n2) out[ob2 + tid] = s;
-        else if (tid == NMAX) out[g.P] = s;
-        else if (tid == NMAX + 1) out[g.P + 1] = s;
+        // db2 | loss sum, valid count: one store at a chosen address (columns n2 .. NMAX - 1 of the sums belong to no output)
+        float *dst = out + (tid < NMAX ? ob2 + tid : g.P + (tid - NMAX));
+        if (tid < n2 || tid >= NMAX) *dst = s;
     }
 }
 

@@ -1,0 +1,276 @@
+#!/usr/bin/env python3
+"""Instruction accounting of the gradient-kernel family's gfx950 machine code (CPU only, no GPU run).
+
+    python scripts/isa_account.py <tag>            -> profiles/isa_account_<tag>.txt
+
+Compiles csrc/learner.hip device-only for gfx950 with _build.FLAGS (minus -shared / -ldl) plus -gline-tables-only, disassembles
+it with source lines (llvm-objdump -d -l) and writes, for k_dqn_grad_packed8<true>, k_dqn_grad_packed8<false>,
+k_dqn_grad_slots<true> and k_dqn_reduce_adam:
+
+  * the instruction count per class (moves, nops, waits, LDS, global, MFMA, other VALU, scalar ALU, scalar memory, branches,
+    lane reads and writes),
+  * the count per segment between workgroup barriers,
+  * the count per source line (top 40; the innermost inlined frame, as the line table gives it),
+  * the runs of six or more consecutive register moves, with their source lines,
+  * the descriptor figures of the metadata note: VGPR, AGPR, SGPR, spills, scratch.
+
+It lists what is in the listing, class by mnemonic prefix; it looks for no particular instruction.  -gline-tables-only changes
+no instruction: the tool checks that by comparing the per-kernel instruction counts with a build without it (--check-lines).
+"""
+from __future__ import annotations
+
+import argparse
+import collections
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from dqn_based_uav_3d_path_planer_amd import _build  # noqa: E402
+
+KERNELS = ["k_dqn_grad_packed8<true>", "k_dqn_grad_packed8<false>", "k_dqn_grad_slots<true>", "k_dqn_reduce_adam"]
+CLASSES = ["move", "nop", "wait", "barrier", "lds", "global", "mfma", "lane", "valu", "smem", "branch", "salu"]
+CLASS_TEXT = {"move": "register moves (v_mov_*)", "nop": "nops (s_nop)", "wait": "waits (s_waitcnt*)", "barrier": "workgroup barriers",
+              "lds": "LDS (ds_*)", "global": "global / flat / buffer / scratch", "mfma": "MFMA (v_mfma_*)",
+              "lane": "lane reads and writes (v_readlane / v_writelane / v_readfirstlane)", "valu": "other VALU (v_*)",
+              "smem": "scalar memory loads (s_load_* / s_buffer_load_*)", "branch": "branches (s_branch / s_cbranch_* / s_setpc / s_endpgm)",
+              "salu": "scalar ALU and the rest (s_*)"}
+
+
+def classify(m: str) -> str:
+    if m.startswith("v_mov_"):
+        return "move"
+    if m == "s_nop":
+        return "nop"
+    if m.startswith("s_waitcnt"):
+        return "wait"
+    if m == "s_barrier":
+        return "barrier"
+    if m.startswith("ds_"):
+        return "lds"
+    if m.startswith(("global_", "flat_", "buffer_", "scratch_")):
+        return "global"
+    if m.startswith(("v_mfma", "v_smfma")):
+        return "mfma"
+    if m.startswith(("v_readlane", "v_writelane", "v_readfirstlane")):
+        return "lane"
+    if m.startswith("v_"):
+        return "valu"
+    if m.startswith(("s_load_", "s_buffer_load_")):
+        return "smem"
+    if m.startswith(("s_branch", "s_cbranch", "s_setpc", "s_swappc", "s_endpgm", "s_call")):
+        return "branch"
+    return "salu"
+
+
+def tool(name: str) -> str:
+    hipcc = _build._hipcc()
+    for d in (os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin"),
+              os.path.join(os.path.dirname(os.path.realpath(hipcc)), "..", "lib", "llvm", "bin"), "/opt/rocm/llvm/bin"):
+        p = os.path.join(d, name)
+        if os.path.exists(p):
+            return p
+    return name
+
+
+def compile_device(src: str, out: str, lines: bool) -> None:
+    flags = [f for f in _build.FLAGS if f not in ("-shared", "-ldl")]
+    cmd = [_build._hipcc()] + flags + (["-gline-tables-only"] if lines else []) + \
+          ["--cuda-device-only", "--no-gpu-bundle-output", "-c", src, "-o", out]
+    subprocess.run(cmd, check=True)
+
+
+def short_name(sym: str) -> str:
+    """'void (anonymous namespace)::k_x<true>((anonymous namespace)::Grad2Args)' -> 'k_x<true>'"""
+    s = sym.replace("(anonymous namespace)::", "")
+    s = re.sub(r"^void ", "", s)
+    depth = 0
+    for i, ch in enumerate(s):                         # cut the argument list: the first '(' outside template brackets
+        if ch == "<":
+            depth += 1
+        elif ch == ">":
+            depth -= 1
+        elif ch == "(" and depth == 0:
+            return s[:i]
+    return s
+
+
+def disassemble(obj: str, lines: bool):
+    """{short kernel name: [(mnemonic, operands, 'file:line' or '')]} for every function symbol of the object"""
+    cmd = [tool("llvm-objdump"), "-d", "--no-show-raw-insn", "-C"] + (["-l"] if lines else []) + [obj]
+    text = subprocess.run(cmd, check=True, capture_output=True, text=True).stdout
+    out, cur, loc = {}, None, ""
+    for ln in text.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.*)>:$", ln)
+        if m:
+            cur = out.setdefault(short_name(m.group(1)), [])
+            loc = ""
+            continue
+        if cur is None or not ln.strip():
+            continue
+        s = ln.strip()
+        if s.startswith(";"):
+            m = re.match(r"^; (\S+):(\d+)$", s)
+            if m:
+                loc = "%s:%s" % (os.path.basename(m.group(1)), m.group(2))
+            continue
+        if s.startswith("...") or s.endswith(":") and " " not in s:
+            continue
+        body = s.split("//")[0].strip()
+        if not body:
+            continue
+        parts = body.split(None, 1)
+        cur.append((parts[0], parts[1] if len(parts) > 1 else "", loc))
+    return out
+
+
+def demangle_map(obj: str) -> dict:
+    """{mangled: demangled} of the object's symbols: the symbol table printed twice, plain and with -C, line for line"""
+    raw = subprocess.run([tool("llvm-objdump"), "-t", obj], check=True, capture_output=True, text=True).stdout.splitlines()
+    dem = subprocess.run([tool("llvm-objdump"), "-t", "-C", obj], check=True, capture_output=True, text=True).stdout.splitlines()
+    out = {}
+    for a, b in zip(raw, dem):
+        m = re.match(r"^[0-9a-f]{16} .{7} \S+\t[0-9a-f]+ (?:\.\w+ )?(.*)$", a)
+        if not m:
+            continue
+        out[m.group(1)] = b[len(a) - len(m.group(1)):]
+    return out
+
+
+def descriptors(obj: str):
+    """{short kernel name: {figure: value}} from the AMDGPU metadata note"""
+    text = subprocess.run([tool("llvm-readelf"), "--notes", obj], check=True, capture_output=True, text=True).stdout
+    keys = {".vgpr_count": "vgpr", ".agpr_count": "agpr", ".sgpr_count": "sgpr", ".vgpr_spill_count": "vgpr_spills",
+            ".sgpr_spill_count": "sgpr_spills", ".private_segment_fixed_size": "scratch", ".group_segment_fixed_size": "static_lds"}
+    kernels, cur = [], None
+    for ln in text.splitlines():
+        m = re.match(r"^  - (\.\w+):\s*(.*)$", ln)                     # a kernel's map begins at a list item of the outer list
+        if m:
+            cur = {}
+            kernels.append(cur)
+        else:
+            m = re.match(r"^    (\.\w+):\s*(.*)$", ln)
+        if not m or cur is None:
+            continue
+        k, v = m.group(1), m.group(2).strip().strip("'")
+        if k in keys:
+            cur[keys[k]] = int(v)
+        elif k == ".name":
+            cur["name"] = v
+    names = demangle_map(obj)
+    return {short_name(names.get(d["name"], d["name"])): d for d in kernels if "name" in d}
+
+
+def account(name: str, ins, desc) -> list:
+    L = []
+    L.append("=" * 100)
+    L.append("%s: %d instructions" % (name, len(ins)))
+    if desc:
+        L.append("  descriptor: vgpr %d  agpr %d  sgpr %d  spills vgpr %d / sgpr %d  scratch %d B  static lds %d B" % (
+            desc.get("vgpr", -1), desc.get("agpr", -1), desc.get("sgpr", -1), desc.get("vgpr_spills", -1), desc.get("sgpr_spills", -1),
+            desc.get("scratch", -1), desc.get("static_lds", -1)))
+    cls = [classify(m) for m, _, _ in ins]
+    # ---- segments between workgroup barriers
+    bars = [i for i, c in enumerate(cls) if c == "barrier"]
+    edges = [0] + bars + [len(ins)]
+    # blocks that the compiler lays out behind the kernel's end (out-of-line arms of earlier branches) are no part of the last
+    # segment's straight-line code: they get a column of their own
+    ends = [i for i, (m, _, _) in enumerate(ins) if m == "s_endpgm" and i > (bars[-1] if bars else -1)]
+    ool = bool(ends) and ends[0] + 1 < len(ins)
+    if ool:
+        edges = edges[:-1] + [ends[0] + 1, len(ins)]
+    seg_name = ["s%d" % k for k in range(len(edges) - 1)]
+    if ool:
+        seg_name[-1] = "ool"
+    L.append("")
+    L.append("  per class, whole kernel and per segment between workgroup barriers (barriers at instruction %s)" % (
+        ", ".join(str(b) for b in bars) or "-"))
+    head = "    %-9s %7s" % ("class", "all") + "".join(" %6s" % n for n in seg_name)
+    L.append(head)
+    for c in CLASSES:
+        row = "    %-9s %7d" % (c, cls.count(c))
+        for k in range(len(edges) - 1):
+            row += " %6d" % cls[edges[k]:edges[k + 1]].count(c)
+        L.append(row)
+    row = "    %-9s %7d" % ("total", len(ins))
+    for k in range(len(edges) - 1):
+        row += " %6d" % (edges[k + 1] - edges[k])
+    L.append(row)
+    L.append("    (segment = instructions [start, end): " + "  ".join(
+        "%s [%d, %d)" % (seg_name[k], edges[k], edges[k + 1]) for k in range(len(edges) - 1)) +
+        ("; ool = blocks laid out behind the kernel's s_endpgm" if ool else "") + ")")
+    # ---- per source line
+    per = collections.Counter(loc or "(no line)" for _, _, loc in ins)
+    mv = collections.Counter(loc or "(no line)" for (_, _, loc), c in zip(ins, cls) if c == "move")
+    L.append("")
+    L.append("  per source line, top 40 (instructions, of which moves)")
+    for loc, n in per.most_common(40):
+        L.append("    %6d %5d  %s" % (n, mv.get(loc, 0), loc))
+    # ---- move runs
+    L.append("")
+    runs, i = [], 0
+    while i < len(ins):
+        if cls[i] == "move":
+            j = i
+            while j < len(ins) and cls[j] == "move":
+                j += 1
+            if j - i >= 6:
+                runs.append((i, j))
+            i = j
+        else:
+            i += 1
+    L.append("  runs of six or more consecutive moves: %d runs, %d moves" % (len(runs), sum(b - a for a, b in runs)))
+    for a, b in runs:
+        seg = max(k for k in range(len(edges) - 1) if edges[k] <= a)
+        locs = collections.Counter(ins[k][2] or "(no line)" for k in range(a, b))
+        L.append("    at %5d (%s) length %2d: %s" % (a, seg_name[seg], b - a, ", ".join("%s x%d" % kv for kv in locs.most_common(4))))
+    L.append("")
+    return L
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("tag")
+    ap.add_argument("--csrc", default=_build.CSRC, help="directory holding learner.hip (default: this tree's csrc)")
+    ap.add_argument("--out", default=None, help="output file (default profiles/isa_account_<tag>.txt)")
+    ap.add_argument("--check-lines", action="store_true", help="also build without -gline-tables-only and compare the counts")
+    args = ap.parse_args()
+    src = os.path.join(args.csrc, "learner.hip")
+    out = args.out or os.path.join(ROOT, "profiles", "isa_account_%s.txt" % args.tag)
+    with tempfile.TemporaryDirectory() as td:
+        obj = os.path.join(td, "learner_lines.o")
+        compile_device(src, obj, True)
+        dis = disassemble(obj, True)
+        desc = descriptors(obj)
+        plain = None
+        if args.check_lines:
+            obj2 = os.path.join(td, "learner_plain.o")
+            compile_device(src, obj2, False)
+            plain = disassemble(obj2, False)
+    flags = " ".join(f for f in _build.FLAGS if f not in ("-shared", "-ldl"))
+    L = ["Instruction accounting of csrc/learner.hip's gradient-kernel family, tag '%s' (scripts/isa_account.py; CPU only)." % args.tag,
+         "  hipcc %s -gline-tables-only --cuda-device-only --no-gpu-bundle-output -c learner.hip" % flags,
+         "  llvm-objdump -d -l --no-show-raw-insn -C ; llvm-readelf --notes",
+         "Counts are instructions proper (labels, source-line comments and the zero padding behind a kernel are not counted).",
+         "Source lines are the innermost inlined frame of the line table.", ""]
+    missing = [k for k in KERNELS if k not in dis]
+    if missing:
+        print("kernels not found in the listing: %s\nhave: %s" % (missing, sorted(dis)), file=sys.stderr)
+        return 1
+    for k in KERNELS:
+        L += account(k, dis[k], desc.get(k))
+        if plain is not None:
+            same = [a[0] for a in plain[k]] == [a[0] for a in dis[k]]
+            L.append("  without -gline-tables-only: %d instructions, mnemonic stream %s" % (len(plain[k]), "identical" if same else "DIFFERENT"))
+            L.append("")
+    with open(out, "w") as f:
+        f.write("\n".join(L))
+    print(out)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
