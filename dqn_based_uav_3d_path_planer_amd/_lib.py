@@ -45,6 +45,7 @@ SYMBOLS = (
     "uavenv_dqn_act_slots", "uavenv_replay_draw_slots", "uavenv_dqn_slots_loop_create", "uavenv_dqn_slots_loop_destroy",
     "uavenv_dqn_slots_loop_set_eps", "uavenv_dqn_slots_loop_run", "uavenv_dqn_slots_loop_get",
     "uavenv_dqn_grad_slots", "uavenv_dqn_reduce_adam_slots", "uavenv_dqn_slots_loop_set_multi_update",
+    "uavenv_fed_choice",
 )
 SAC_CRITIC_IN, SAC_ACTOR_PARAMS, SAC_CRITIC_PARAMS, SAC_ACTOR_STRIDE, SAC_CRITIC_STRIDE = 102, 6724, 10882, 6728, 21768
 
@@ -154,6 +155,7 @@ class UavSacAdam(C.Structure):
 
 SAC_LOOP_MAX_SLOTS = 8
 FED_MAX_BLOCKS = 8
+FED_CHOICE_MAX_STATES = 16   # uavenv_fed_choice: one 16-row MFMA strip of replayed states per UAV
 DRAW_MAX_TRIES = 8
 DQN_IMAGE_FLOATS = 6912      # csrc/dqn_internal.hpp
 
@@ -450,6 +452,8 @@ def load() -> C.CDLL:
     lib.uavenv_per_fill_frame_strided.argtypes = [per, i64, i64, f64, vp, i64, i64, vp]
     lib.uavenv_fed_aggregate.restype = C.c_int
     lib.uavenv_fed_aggregate.argtypes = [vp, i32, i32, f32, vp]
+    lib.uavenv_fed_choice.restype = C.c_int
+    lib.uavenv_fed_choice.argtypes = [vp, i32, i32, vp, i32, C.POINTER(C.POINTER(UavDqnNet)), i32, vp, vp, vp, vp]
     lib.uavenv_eval_episodes.restype = C.c_int
     lib.uavenv_eval_episodes.argtypes = [vp, C.POINTER(UavDqnNet), C.POINTER(UavEvalArgs), vp]
     lib.uavenv_eval_episodes_slots.restype = C.c_int

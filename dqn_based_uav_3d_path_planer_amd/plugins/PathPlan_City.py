@@ -149,7 +149,8 @@ class PathPlan_City:
         self.Is_FL = int(None2Value(param.get("Is_FL"), 0))
         self.FL_Loop = int(None2Value(param.get("FL_Loop"), 3))
         # <FL_Aggregate>: "reference" (default) = the merge as the reference executes it -- the SUM of the UAVs' models: its
-        # division at Envs/PathPlan_City.py:597 never reaches the model -- or "mean" (dqn_based_uav_3d_path_planer_amd/federated.py)
+        # division at Envs/PathPlan_City.py:597 never reaches the model --, "mean", or "choice" = the selective merge of
+        # Federated_Learning_choice (:644-684), DQN-family trainers only (dqn_based_uav_3d_path_planer_amd/federated.py)
         self.FL_Aggregate = str(None2Value(param.get("FL_Aggregate"), "reference"))
         # (absent: the actor-critic merge keeps the executed reference's SUM and says so once; the DQN-family merge, for which the
         # reference has no executed behaviour -- its Federated_Learning raises AttributeError -- takes the mean: a SUM of U
@@ -157,9 +158,16 @@ class PathPlan_City:
         self._fl_aggregate_given = param.get("FL_Aggregate") is not None
         self._fl_warned = False
         from dqn_based_uav_3d_path_planer_amd import federated as _fed
-        if self.FL_Aggregate not in _fed.AGGREGATES:
-            raise ValueError(f"<FL_Aggregate>{self.FL_Aggregate}</FL_Aggregate>: expected one of {_fed.AGGREGATES}")
+        if self.FL_Aggregate not in _fed.AGGREGATES + _fed.SELECTIVE:
+            raise ValueError(f"<FL_Aggregate>{self.FL_Aggregate}</FL_Aggregate>: expected one of {_fed.AGGREGATES + _fed.SELECTIVE}")
+        # "choice": the selective merge the reference executes for DQN-family trainers (Federated_Learning_choice, :644-684)
+        if self.FL_Aggregate in _fed.SELECTIVE and self.Is_AC:
+            raise ValueError(f"<FL_Aggregate>{self.FL_Aggregate}</FL_Aggregate> merges q_local (Envs/PathPlan_City.py:649-683): "
+                             "it needs DQN-family trainers (Is_AC = 0)")
         self.fl_merges = 0             # federated merges done so far (diagnostics / tests)
+        self.fl_skipped = 0            # selective merges skipped: a UAV's replay held fewer than 10 valid transitions
+        self.fl_chosen = None          # the last selective merge's chosen lists (a device tensor on the fused-slots path)
+        self._fl_slot_valid = [0] * self.num_UAV     # valid transitions each slot has written (fused-slots path)
         self.executed_time = 0
         self._state_cache = None
         self._state0 = None
@@ -506,11 +514,42 @@ class PathPlan_City:
         self.fl_merged_on = federated.federated_learning_q([u.Trainer for u in self.Agents],
                                                            self.FL_Aggregate if self._fl_aggregate_given else "mean")
 
+    def Federated_Learning_choice(self):
+        """Envs/PathPlan_City.py:644-684, the selective merge (<FL_Aggregate>choice</FL_Aggregate>): in UAV order, each UAV
+        averages its q_local with the (num_UAV - 1) // 2 others whose Q-values on 10 of ITS replayed states are closest.
+        Fused slots: the pairs come from one draw over the valid rows of the ring (key derived from <seed>, counter = merges done
+        so far) and the merge is one launch on ring.obs -- nothing is read back; otherwise 10 rows of every trainer's
+        VecReplayMemory, drawn with torch's generator in UAV order before the merge, through torch.
+        -> False (and fl_skipped counts it) when a UAV's replay holds fewer than 10 valid transitions: the reference's
+        random.sample raises there."""
+        from dqn_based_uav_3d_path_planer_amd import federated
+        trs = [u.Trainer for u in self.Agents]
+        S, info = federated.CHOICE_STATES, {}
+        if self.fast_slots:
+            if self._ring.filled <= 0 or min(self._fl_slot_valid) < S:
+                self.fl_skipped += 1
+                return False
+            pairs = federated.draw_slot_pairs(self._ring, self.num_UAV, S, self.seed * 1000003 + 0xF1C, self.fl_merges)
+            self.fl_merged_on = federated.federated_learning_choice(trs, obs=self._ring.obs, pairs=pairs, info=info)
+        else:
+            mems = [t.replay_memory for t in trs]
+            if any(not hasattr(m, "states") or m.size < S for m in mems):
+                self.fl_skipped += 1
+                return False
+            states = [m.states[torch.randperm(m.size, device=m.device)[:S]] for m in mems]
+            self.fl_merged_on = federated.federated_learning_choice(trs, states=states, info=info)
+        self.fl_chosen = info.get("chosen")
+        self._fl_info = info
+        return True
+
     def _federated_merge(self):
         """:469-475, after epoch += 1: every FL_Loop episodes when Is_FL."""
         if self.Is_FL and self.FL_Loop > 0 and self.epoch % self.FL_Loop == 0:
             if self.Is_AC:
                 self.Federated_Learning_AC()
+            elif self.FL_Aggregate == "choice":
+                if not self.Federated_Learning_choice():
+                    return
             else:
                 self.Federated_Learning()
             self.fl_merges += 1
@@ -655,7 +694,8 @@ class PathPlan_City:
             fr = (t0 + torch.arange(k, device=dev)) % ring.frames
             v = ring.valid[fr].bool()                                                # [k, N] agents moved by each step
             inf = self._info[fr]
-            stats = torch.stack([v.sum(1)] + [((inf == c) & v).sum(1) for c in range(3)], 1).cpu().numpy()   # one sync
+            stats = torch.cat([torch.stack([v.sum(1)] + [((inf == c) & v).sum(1) for c in range(3)], 1),
+                               v.view(k, -1, U).sum(1)], 1).cpu().numpy()            # one sync; columns 4..: moved per UAV slot
             for i in range(k):
                 if stats[i, 0] == 0:                                                 # nobody moved: finished before this step
                     ended = True
@@ -664,6 +704,8 @@ class PathPlan_City:
                 self.result["normal"] += int(stats[i, 1])
                 self.result["success"] += int(stats[i, 2])
                 self.result["lose"] += int(stats[i, 3])
+                for j in range(U):                                                   # (the selective merge's 10-transition rule)
+                    self._fl_slot_valid[j] += int(stats[i, 4 + j])
             self._obs_raw = ring.obs[ring.head]
             self._invalidate()
             if self.record_path:

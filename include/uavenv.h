@@ -948,6 +948,25 @@ int uavenv_dqn_slots_loop_get(const UavDqnSlotsLoop *loop, UavDqnSlotsLoopCursor
 #define UAVENV_FED_MAX_BLOCKS 8
 int uavenv_fed_aggregate(float *const *blocks, int32_t n_blocks, int32_t n_floats, float scale, void *stream);
 
+/* ---- selective federated merge of DQN-family slot learners (Federated_Learning_choice, Envs/PathPlan_City.py:644-684) ----------
+ * For p = 0 .. n_nets-1 IN ORDER, each step on the blocks as the earlier steps left them: q_local of nets[p] (host array, as
+ * uavenv_dqn_act_slots takes it) and of every other net are forwarded (f32 MFMA) on net p's n_states packed rows
+ * obs_dev[frame][agent] named by pairs_dev[p][s] = (frame, agent) -- uavenv_replay_draw_slots' layout --,
+ * d[p][j] = mean((q_p - q_j)^2) over all n_states x n_actions elements (f32), the others are sorted by d ascending, stably (ties
+ * keep the index order), the first (n_nets - 1) / 2 are chosen, and nets[p]->local <- (w_p + w_c0 + w_c1 + ...) / (k + 1): f32
+ * adds in chosen order, then a correctly rounded division.  Only `local` blocks are written (replace_param,
+ * Trainer/DuelingDQN_Trainer.py:204-207): targets and Adam moments stay.  One launch of one workgroup; never synchronises.
+ * dist_out_dev (nullable, [n_nets][n_nets] f32, row p as step p computed it, 0 on the diagonal) and chosen_out_dev (nullable,
+ * [n_nets][n_nets] int32, row p = the chosen indices in order, padded with -1) are diagnostics.
+ * *status_out_dev (mandatory) <- 0, or 1 when any pair is out of range (0 <= frame < frames, 0 <= agent < n_agents): then NO block
+ * is written (nor dist / chosen) -- an out-of-range index never becomes an address.
+ * UAVENV_EINVAL, with nothing enqueued, for: n_nets outside 1..UAVENV_DQN_MAX_SLOTS; n_states outside 1..16; a NULL net, obs, pairs
+ * or status pointer; a `local` block or obs_dev off 16 bytes; two nets sharing a `local` block; an f16-MFMA net; nets that differ in
+ * n_actions or dueling; a head uavenv_dqn_act_slots refuses; frames <= 0 or n_agents <= 0. */
+int uavenv_fed_choice(const void *obs_dev, int32_t frames, int32_t n_agents, const int32_t *pairs_dev, int32_t n_states,
+                      const UavDqnNet *const *nets, int32_t n_nets, float *dist_out_dev, int32_t *chosen_out_dev,
+                      int32_t *status_out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
