@@ -137,7 +137,8 @@ int uavenv_bank_stats(const UavEnv *env, int32_t *m, int32_t *replaced);
  *                         reset EVERY agent (uavenv_reset_all: an episode boundary of the plugin path), so no list is in use
  *                         and every usable plan is taken.
  *   uavenv_replan_stats   out5 = {refreshes begun, rows planned, rows committed, rows skipped: in use, rows skipped: no plan}
- *                         (synchronises). */
+ *                         (synchronises).  Every row of a committed slice is counted once; a row that is both in use and
+ *                         without a usable plan counts as "in use" (under force no row is in use). */
 int uavenv_replan_begin(UavEnv *env, int32_t first, int32_t count, uint64_t seed, int32_t max_iter, void *plan_stream);
 int uavenv_replan_ready(UavEnv *env);
 int uavenv_replan_commit(UavEnv *env, int32_t force, void *stream);
