@@ -185,6 +185,13 @@ int uavenv_get_state(UavEnv *env, int32_t first, int32_t count, double *out16, d
  *   energy64      Calc_Fly_Power at the post-step speed (UAV.py:239-245), J per unit-time step
  *   active        nullable N-byte mask; agents with 0 are left untouched (info SKIPPED, valid 0) -- this is how
  *                 BaseEnv.Move_Agent(index, action) moves ONE agent of the batch
+ * Teams (uav_per_env = U > 1; agent i is UAV i mod U of env i / U; held to oracle/team_model.py by
+ * tests/test_team_protocol_gpu.py): an agent that is done and waits (SKIP_DONE) or that `active` leaves out reports
+ * info SKIPPED, valid 0, ret_done = agent_done = its done flag, reward 0, and its state is not written.  Under AUTO_RESET the
+ * env restarts in the launch after which all U of its agents are done: a masked agent that is done counts towards that, a
+ * masked agent that is not done blocks it.  The restart re-draws EVERY agent of the env in that launch -- waiting and masked
+ * ones too (their outputs still describe them as skipped; obs is the fresh state's).  Without SKIP_DONE a done agent
+ * steps on (and stays done); the env still restarts only when complete.  energy64 uses UAV (i mod U)'s A and xi.
  */
 int uavenv_step(UavEnv *env, const void *actions_dev, int32_t action_kind, void *obs_dev, double *reward64_dev,
                 float *reward32_dev, uint8_t *ret_done_dev, uint8_t *agent_done_dev, uint8_t *info_dev,
