@@ -13,7 +13,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libuavenv.so")
 SOURCES = ["uavenv.hip", "replay.hip", "learner.hip", "rrt.hip", "per.hip", "loop.hip", "p2p.hip", "coll.hip", "sac.hip", "fed.hip"]
-HEADERS = ["uavenv_device.hpp", "qnet_device.hpp", "dqn_internal.hpp", "dqn_slots_internal.hpp", os.path.join("..", "..", "include", "uavenv.h")]
+HEADERS = ["uavenv_device.hpp", "qnet_device.hpp", "dqn_internal.hpp", "dqn_slots_internal.hpp", "grad_packed8_body.inc", "reduce_adam_body.inc",
+           os.path.join("..", "..", "include", "uavenv.h")]
 # -ffp-contract=off: the reward / collision arithmetic must round like the reference's
 # separate multiplies and adds (no FMA fusion); see csrc/uavenv_device.hpp.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",

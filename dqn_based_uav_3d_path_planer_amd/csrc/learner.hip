@@ -527,6 +527,29 @@ struct GradLdsP {
     float *W1l, *W1t, *Hs, *dHs, *douts, *W2l, *W2t, *b2l, *b2t, *red;
     uint32_t *Ps;                    // [64][20] packed rows of s (+ 4 dwords of pad)
 };
+// Where GradLdsP's regions start, in floats from the start of the dynamic LDS: the one list that the carve-up and the launch sizes
+// (kGradPLds, kGradP8Lds) are both made from
+constexpr int kPoW1l = 0;                              // [64][108] local fc1 (+ b1 in column 100)
+constexpr int kPoW1t = kPoW1l + kTileF;                // target fc1
+constexpr int kPoHs = kPoW1t + kTileF;                 // [64][68] relu(fc1(s))
+constexpr int kPoDHs = kPoHs + kTile * kLh;            // [64][68] dL/dH
+constexpr int kPoDouts = kPoDHs + kTile * kLh;         // [64][16] dL/d(layer-2 output)
+constexpr int kPoW2l = kPoDouts + kTile * kMaxOut;     // [16][64]
+constexpr int kPoW2t = kPoW2l + kMaxOut * kHid;
+constexpr int kPoB2l = kPoW2t + kMaxOut * kHid;        // [16]
+constexpr int kPoB2t = kPoB2l + kMaxOut;
+constexpr int kPoRed = kPoB2t + kMaxOut;               // [4][18] per-wave column sums
+constexpr int kPoPs = kPoRed + 4 * (kMaxOut + 2);      // the packed rows (25 704 floats in)
+constexpr int kPoEnd = kPoPs + kTile * kPackedDwords + 4;      // k_dqn_grad_packed's LDS ends here; the packed8 family's qn follows
+static_assert(kPoPs % 4 == 0, "packed-row staging must start 16-byte aligned");
+constexpr size_t kGradPLds = (size_t)kPoEnd * 4;
+constexpr size_t kGradP8Lds = (size_t)(kPoEnd + kTile + 4) * 4;        // + qn: 64 bootstrap values, the 4 strips' max |dH|
+
+__device__ __forceinline__ GradLdsP grad_ldsp(float *lds)
+{
+    return GradLdsP{lds + kPoW1l, lds + kPoW1t, lds + kPoHs, lds + kPoDHs, lds + kPoDouts, lds + kPoW2l, lds + kPoW2t,
+                    lds + kPoB2l, lds + kPoB2t, lds + kPoRed, reinterpret_cast<uint32_t *>(lds + kPoPs)};
+}
 
 template <int NMAX, bool FIRST>
 __device__ __forceinline__ void grad_tile_packed(const GradArgs &g, const GradLdsP &L, int tile, bool more, GradAcc<NMAX> &A)
@@ -690,18 +713,7 @@ __global__ void __launch_bounds__(256) k_dqn_grad_packed(Grad2Args ga)
 {
     const GradArgs &g = ga.g;
     extern __shared__ __align__(16) float lds[];
-    GradLdsP L;
-    L.W1l = lds;                            // [64][108] local fc1 (+ b1 in column 100)
-    L.W1t = L.W1l + kTileF;                 // target fc1
-    L.Hs = L.W1t + kTileF;                  // [64][68] relu(fc1(s))
-    L.dHs = L.Hs + kTile * kLh;             // [64][68] dL/dH
-    L.douts = L.dHs + kTile * kLh;          // [64][16] dL/d(layer-2 output)
-    L.W2l = L.douts + kTile * kMaxOut;      // [16][64]
-    L.W2t = L.W2l + kMaxOut * kHid;
-    L.b2l = L.W2t + kMaxOut * kHid;         // [16]
-    L.b2t = L.b2l + kMaxOut;
-    L.red = L.b2t + kMaxOut;                // [4][18] per-wave column sums
-    L.Ps = reinterpret_cast<uint32_t *>(L.red + 4 * (kMaxOut + 2));          // 16-byte aligned (25 704 floats in)
+    const GradLdsP L = grad_ldsp(lds);
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 15, gq = lane >> 4;
     const int n2 = g.n_actions + (g.dueling ? 1 : 0);
     GradAcc<NMAX> A;
@@ -976,91 +988,21 @@ __device__ __forceinline__ void grad_tile_packed8(const GradArgs &g, const GradL
     if (more) __syncthreads();                        // the next tile overwrites Ps / Hs / dHs / douts / qn
 }
 
+#define UAV_ROW_ST4(ptr, val) (*reinterpret_cast<floatx4 *>(ptr) = (val))
+
 template <bool GLDS>
 __global__ void __launch_bounds__(512) k_dqn_grad_packed8(Grad2Args ga)
 {
     UAV_HOT_PRIO();
-    constexpr int NMAX = 4;
     const GradArgs &g = ga.g;
-    extern __shared__ __align__(16) float lds[];
-    GradLdsP L;
-    L.W1l = lds;
-    L.W1t = L.W1l + kTileF;
-    L.Hs = L.W1t + kTileF;
-    L.dHs = L.Hs + kTile * kLh;
-    L.douts = L.dHs + kTile * kLh;
-    L.W2l = L.douts + kTile * kMaxOut;
-    L.W2t = L.W2l + kMaxOut * kHid;
-    L.b2l = L.W2t + kMaxOut * kHid;
-    L.b2t = L.b2l + kMaxOut;
-    L.red = L.b2t + kMaxOut;
-    L.Ps = reinterpret_cast<uint32_t *>(L.red + 4 * (kMaxOut + 2));
-    float *qn_lds = reinterpret_cast<float *>(L.Ps + kTile * kPackedDwords + 4);
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), grp = wv >> 2, strip = wv & 3;
-    const int r = lane & 15, gq = lane >> 4;
-    const int n2 = g.n_actions + (g.dueling ? 1 : 0);
-    GradAcc8 A;
-#pragma unroll
-    for (int u = 0; u < 6; ++u) A.acc[u] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int a = 0; a < 6; ++a) A.csum[a] = 0.0f;
-    L_STAMP(0);
-    const int step = (int)gridDim.x;
-    int tile = (int)blockIdx.x;
-    grad_tile_packed8<true, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
-    for (tile += step; tile < ga.n_tiles; tile += step)
-        grad_tile_packed8<false, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
-    L_STAMP(5);
-    // ---- the partial-gradient row of this workgroup: dW1 | db1 | dW2 | db2 | loss sum | valid count
-    float *out = g.partials + (size_t)blockIdx.x * ga.stride;
-    const int oW2 = kHid * kW + kHid, ob2 = oW2 + n2 * kHid;
-    const int j = 16 * strip + r;
-    // (round 5, measured: non-temporal stores of the row lengthen this kernel by 0.8 us and shorten the next by as much -- the 6.8 MB
-    // of partial rows cross the memory system once either way)
-#define UAV_ROW_ST4(ptr, val) (*reinterpret_cast<floatx4 *>(ptr) = (val))
-    // (grad_products_split8's register layout) group 1: acc[u] = tile u of the flag columns (exact zeros at the scalar columns, which
-    // group 0 stores from its gathered tile: columns 0..10 and 86..89 are left out here); group 0: acc[0] = the gathered tile
-    // (entries 0..10 = columns 0..10, 11..14 = 86..89, 15 = db1), acc[1] = dW2^T; columns 96..99 are constant zero
-    if (grp == 1) {
-        float *t0 = out + j * kW + 4 * gq;
-        if (gq == 3) UAV_ROW_ST4(t0, A.acc[0]);                      // columns 12..15
-        else if (gq == 2) t0[3] = A.acc[0][3];                       // column 11
-#pragma unroll
-        for (int u = 1; u < 5; ++u) UAV_ROW_ST4(out + j * kW + 16 * u + 4 * gq, A.acc[u]);
-        float *t5 = out + j * kW + 80 + 4 * gq;
-        if (gq == 0 || gq == 3) UAV_ROW_ST4(t5, A.acc[5]);
-        else {                                                       // columns 84, 85 (gq 1) / 90, 91 (gq 2): one 8-byte store of the chosen half
-            const int h = 2 * (gq - 1);
-            *reinterpret_cast<float2 *>(t5 + h) = gq == 1 ? make_float2(A.acc[5][0], A.acc[5][1]) : make_float2(A.acc[5][2], A.acc[5][3]);
-        }
-    } else {
-        const floatx4 sc = A.acc[0];
-        if (gq < 2) UAV_ROW_ST4(out + j * kW + 4 * gq, sc);                                            // columns 0..7
-        else if (gq == 2) { out[j * kW + 8] = sc[0]; out[j * kW + 9] = sc[1]; out[j * kW + 10] = sc[2]; out[j * kW + 86] = sc[3]; }
-        else { out[j * kW + 87] = sc[0]; out[j * kW + 88] = sc[1]; out[j * kW + 89] = sc[2]; out[kHid * kW + j] = sc[3]; }
-        if (gq == 0) UAV_ROW_ST4(out + j * kW + 96, (floatx4{0.0f, 0.0f, 0.0f, 0.0f}));
-        if (r < n2) UAV_ROW_ST4(out + oW2 + r * kHid + 16 * strip + 4 * gq, A.acc[1]);                  // dW2^T
-    }
-    if (grp == 0 && lane == 0) {
-#pragma unroll
-        for (int a = 0; a < NMAX + 2; ++a) L.red[strip * (kMaxOut + 2) + a] = A.csum[a];
-    }
-    __syncthreads();
-    if (tid < NMAX + 2) {
-        const float s = (L.red[tid] + L.red[(kMaxOut + 2) + tid]) + (L.red[2 * (kMaxOut + 2) + tid] + L.red[3 * (kMaxOut + 2) + tid]);
-        // db2 | loss sum, valid count: one store at a chosen address (columns n2 .. NMAX - 1 of the sums belong to no output)
-        float *dst = out + (tid < NMAX ? ob2 + tid : g.P + (tid - NMAX));
-        if (tid < n2 || tid >= NMAX) *dst = s;
-    }
+#include "grad_packed8_body.inc"
 }
 
 // One learner per UAV slot in ONE launch: slice blockIdx.y of the grid is k_dqn_grad_packed8 for slot y -- its nets, its layer-1 image,
 // its (frame, agent) pairs, its partial rows, picked from the table in the kernel arguments by the wavefront-uniform blockIdx.y
-// (scalar loads: no VGPR holds a slot's pointer).  The ring and every hyper-parameter are the slots' common ones.  Same device
-// functions in the same order: workgroup (x, y) writes the row that workgroup x of k_dqn_grad_packed8 writes for slot y, bit for bit.
-// The kernel-level body (LDS carve-up, tile loop, partial-row writer) is k_dqn_grad_packed8's text again rather than a function both
-// call: with the body behind a call that kernel came out of the compiler with the same registers but another instruction stream, and
-// the single-learner loops are timed on it.
+// (scalar loads: no VGPR holds a slot's pointer).  The ring and every hyper-parameter are the slots' common ones.  Everything behind
+// that prelude is grad_packed8_body.inc, the one text of both kernels (see there why it is text): workgroup (x, y) writes the row
+// that workgroup x of k_dqn_grad_packed8 writes for slot y, bit for bit.
 constexpr int kActMaxSlots = 8;            // (= UAVENV_DQN_MAX_SLOTS: every per-slot table of kernel arguments)
 struct GradSlotsArgs {
     Grad2Args ga;                    // g.local / target / img / partials / explicit_idx are taken from slot[] below; no is_w / abs_td / dbg
@@ -1085,83 +1027,8 @@ __global__ void __launch_bounds__(512) k_dqn_grad_slots(GradSlotsArgs sa)
     g.abs_td = nullptr;
     g.dbg = nullptr;
     const Grad2Args &ga = sa.ga;
-    constexpr int NMAX = 4;
-    extern __shared__ __align__(16) float lds[];
-    GradLdsP L;
-    L.W1l = lds;
-    L.W1t = L.W1l + kTileF;
-    L.Hs = L.W1t + kTileF;
-    L.dHs = L.Hs + kTile * kLh;
-    L.douts = L.dHs + kTile * kLh;
-    L.W2l = L.douts + kTile * kMaxOut;
-    L.W2t = L.W2l + kMaxOut * kHid;
-    L.b2l = L.W2t + kMaxOut * kHid;
-    L.b2t = L.b2l + kMaxOut;
-    L.red = L.b2t + kMaxOut;
-    L.Ps = reinterpret_cast<uint32_t *>(L.red + 4 * (kMaxOut + 2));
-    float *qn_lds = reinterpret_cast<float *>(L.Ps + kTile * kPackedDwords + 4);
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), grp = wv >> 2, strip = wv & 3;
-    const int r = lane & 15, gq = lane >> 4;
-    const int n2 = g.n_actions + (g.dueling ? 1 : 0);
-    GradAcc8 A;
-#pragma unroll
-    for (int u = 0; u < 6; ++u) A.acc[u] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int a = 0; a < 6; ++a) A.csum[a] = 0.0f;
-    L_STAMP(0);
-    const int step = (int)gridDim.x;
-    int tile = (int)blockIdx.x;
-    grad_tile_packed8<true, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
-    for (tile += step; tile < ga.n_tiles; tile += step)
-        grad_tile_packed8<false, GLDS>(g, L, qn_lds, tile, tile + step < ga.n_tiles, A);
-    L_STAMP(5);
-    // ---- the partial-gradient row of this workgroup: dW1 | db1 | dW2 | db2 | loss sum | valid count
-    float *out = g.partials + (size_t)blockIdx.x * ga.stride;
-    const int oW2 = kHid * kW + kHid, ob2 = oW2 + n2 * kHid;
-    const int j = 16 * strip + r;
-    // (grad_products_split8's register layout) group 1: acc[u] = tile u of the flag columns (exact zeros at the scalar columns, which
-    // group 0 stores from its gathered tile: columns 0..10 and 86..89 are left out here); group 0: acc[0] = the gathered tile
-    // (entries 0..10 = columns 0..10, 11..14 = 86..89, 15 = db1), acc[1] = dW2^T; columns 96..99 are constant zero
-    if (grp == 1) {
-        float *t0 = out + j * kW + 4 * gq;
-        if (gq == 3) UAV_ROW_ST4(t0, A.acc[0]);                      // columns 12..15
-        else if (gq == 2) t0[3] = A.acc[0][3];                       // column 11
-#pragma unroll
-        for (int u = 1; u < 5; ++u) UAV_ROW_ST4(out + j * kW + 16 * u + 4 * gq, A.acc[u]);
-        float *t5 = out + j * kW + 80 + 4 * gq;
-        if (gq == 0 || gq == 3) UAV_ROW_ST4(t5, A.acc[5]);
-        else {                                                       // columns 84, 85 (gq 1) / 90, 91 (gq 2): one 8-byte store of the chosen half
-            const int h = 2 * (gq - 1);
-            *reinterpret_cast<float2 *>(t5 + h) = gq == 1 ? make_float2(A.acc[5][0], A.acc[5][1]) : make_float2(A.acc[5][2], A.acc[5][3]);
-        }
-    } else {
-        const floatx4 sc = A.acc[0];
-        if (gq < 2) UAV_ROW_ST4(out + j * kW + 4 * gq, sc);                                            // columns 0..7
-        else if (gq == 2) { out[j * kW + 8] = sc[0]; out[j * kW + 9] = sc[1]; out[j * kW + 10] = sc[2]; out[j * kW + 86] = sc[3]; }
-        else { out[j * kW + 87] = sc[0]; out[j * kW + 88] = sc[1]; out[j * kW + 89] = sc[2]; out[kHid * kW + j] = sc[3]; }
-        if (gq == 0) UAV_ROW_ST4(out + j * kW + 96, (floatx4{0.0f, 0.0f, 0.0f, 0.0f}));
-        if (r < n2) UAV_ROW_ST4(out + oW2 + r * kHid + 16 * strip + 4 * gq, A.acc[1]);                  // dW2^T
-    }
-    if (grp == 0 && lane == 0) {
-#pragma unroll
-        for (int a = 0; a < NMAX + 2; ++a) L.red[strip * (kMaxOut + 2) + a] = A.csum[a];
-    }
-    __syncthreads();
-    if (tid < NMAX + 2) {
-        const float s = (L.red[tid] + L.red[(kMaxOut + 2) + tid]) + (L.red[2 * (kMaxOut + 2) + tid] + L.red[3 * (kMaxOut + 2) + tid]);
-        // db2 | loss sum, valid count: one store at a chosen address (columns n2 .. NMAX - 1 of the sums belong to no output)
-        float *dst = out + (tid < NMAX ? ob2 + tid : g.P + (tid - NMAX));
-        if (tid < n2 || tid >= NMAX) *dst = s;
-    }
+#include "grad_packed8_body.inc"
 }
-
-constexpr size_t kGradP8Lds = (size_t)(2 * kTileF + 2 * kTile * kLh + kTile * kMaxOut + 2 * kMaxOut * kHid + 2 * kMaxOut +
-                                       4 * (kMaxOut + 2) + kTile * kPackedDwords + 4 + kTile + 4) * 4;      // (+ 4: the strips' max |dH|)
-
-constexpr size_t kGradPLds = (size_t)(2 * kTileF + 2 * kTile * kLh + kTile * kMaxOut + 2 * kMaxOut * kHid + 2 * kMaxOut +
-                                      4 * (kMaxOut + 2) + kTile * kPackedDwords + 4) * 4;
-static_assert((2 * kTileF + 2 * kTile * kLh + kTile * kMaxOut + 2 * kMaxOut * kHid + 2 * kMaxOut + 4 * (kMaxOut + 2)) % 4 == 0,
-              "packed-row staging must start 16-byte aligned");
 
 // =====================================================================================================================
 // f16 MFMA learner (UavDqnNet.mfma_dtype = 1; BASELINE configs[2]: "fp16 Q-net MFMA").
@@ -1681,49 +1548,13 @@ __global__ void __launch_bounds__(256) k_dqn_reduce_adam(const float *__restrict
                                                          int hard_update, float *__restrict__ loss, float *__restrict__ raw,
                                                          const uint32_t *__restrict__ go_word, uint32_t go_value, float *__restrict__ img)
 {
-    // gated update (uavenv_dqn_reduce_adam_gated): the step kernel of this pass stamps go_word with go_value when it moved at
-    // least one agent; a pass in which every agent had already finished leaves the learner exactly as it is (the reference's loop
-    // has left run_eposide by then, Envs/PathPlan_City.py:456-459)
-    UAV_HOT_PRIO();
-    if (go_word && __hip_atomic_load(go_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != go_value) return;
-    __shared__ float cnt_part[4];
-    const int tid = (int)threadIdx.x;
-    const int p = (int)blockIdx.x * 32 + tid;
-    // this parameter's moments and value are requested FIRST: their round trip runs under the partial rows' (behind the
-    // reduction's barriers they were a second, dependent round trip of the launch)
-    float m0 = 0.0f, v0 = 0.0f, w0 = 0.0f;
-    if (tid < 32 && p < P) { m0 = m[p]; v0 = v[p]; w0 = local[p]; }
-    float c;
-    const float t = reduce_columns(partials, nblk, P, stride, c);
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((tid & 63) == 0) cnt_part[tid >> 6] = c;
-    __syncthreads();
-    const float cnt = (cnt_part[0] + cnt_part[1]) + (cnt_part[2] + cnt_part[3]);
-    const float inv = 1.0f / (cnt > 1.0f ? cnt : 1.0f);
-    if (tid < 32 && p < P + 2) {
-        if (raw) raw[p] = t;
-        if (p < P) {
-            const float gp = t * inv;
-            const float mp = m0 + (gp - m0) * (1.0f - beta1);
-            const float vp = v0 * beta2 + (1.0f - beta2) * gp * gp;
-            m[p] = mp;
-            v[p] = vp;
-            const float np = w0 - (lr / bc1) * (mp / (sqrtf(vp) / bc2_sqrt + eps));
-            local[p] = np;
-            if (hard_update) target[p] = np;
-            if (img) {                        // the C loop's layer-1 image follows the parameters (qnet_device.hpp: img_store_param)
-                img_store_param(img, p, np);
-                if (hard_update) img_store_param(img + kSplitF, p, np);
-            }
-        } else if (p == P && loss) {
-            *loss = t * inv;
-        }
-    }
+#include "reduce_adam_body.inc"
 }
 
 // The same for one learner per UAV slot in ONE launch: slice blockIdx.y of the grid is k_dqn_reduce_adam for slot y (its partial rows,
 // blocks, loss cell, image, bias corrections and hard-copy flag from the table; the slots' update counts may differ).  Same summation
-// order (reduce_columns), same Adam arithmetic: bit for bit the per-slot launch.  One gate for all slots.
+// order (reduce_columns), same Adam arithmetic -- reduce_adam_body.inc, the one text of both kernels: bit for bit the per-slot launch.
+// One gate for all slots.
 struct AdamSlotsArgs {
     int nblk, P, stride;
     float lr, beta1, beta2, eps;
@@ -1747,42 +1578,7 @@ __global__ void __launch_bounds__(256) k_dqn_reduce_adam_slots(AdamSlotsArgs a)
     const uint32_t go_value = a.go_value;
     const int nblk = a.nblk, P = a.P, stride = a.stride, hard_update = sl.hard_update;
     const float lr = a.lr, beta1 = a.beta1, beta2 = a.beta2, eps = a.eps, bc1 = sl.bc1, bc2_sqrt = sl.bc2_sqrt;
-    // (from here k_dqn_reduce_adam's text: that kernel stays as the compiler made it, see k_dqn_grad_slots)
-    UAV_HOT_PRIO();
-    if (go_word && __hip_atomic_load(go_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != go_value) return;
-    __shared__ float cnt_part[4];
-    const int tid = (int)threadIdx.x;
-    const int p = (int)blockIdx.x * 32 + tid;
-    // this parameter's moments and value are requested FIRST: their round trip runs under the partial rows' (behind the
-    // reduction's barriers they were a second, dependent round trip of the launch)
-    float m0 = 0.0f, v0 = 0.0f, w0 = 0.0f;
-    if (tid < 32 && p < P) { m0 = m[p]; v0 = v[p]; w0 = local[p]; }
-    float c;
-    const float t = reduce_columns(partials, nblk, P, stride, c);
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((tid & 63) == 0) cnt_part[tid >> 6] = c;
-    __syncthreads();
-    const float cnt = (cnt_part[0] + cnt_part[1]) + (cnt_part[2] + cnt_part[3]);
-    const float inv = 1.0f / (cnt > 1.0f ? cnt : 1.0f);
-    if (tid < 32 && p < P + 2) {
-        if (raw) raw[p] = t;
-        if (p < P) {
-            const float gp = t * inv;
-            const float mp = m0 + (gp - m0) * (1.0f - beta1);
-            const float vp = v0 * beta2 + (1.0f - beta2) * gp * gp;
-            m[p] = mp;
-            v[p] = vp;
-            const float np = w0 - (lr / bc1) * (mp / (sqrtf(vp) / bc2_sqrt + eps));
-            local[p] = np;
-            if (hard_update) target[p] = np;
-            if (img) {                        // the C loop's layer-1 image follows the parameters (qnet_device.hpp: img_store_param)
-                img_store_param(img, p, np);
-                if (hard_update) img_store_param(img + kSplitF, p, np);
-            }
-        } else if (p == P && loss) {
-            *loss = t * inv;
-        }
-    }
+#include "reduce_adam_body.inc"
 }
 
 struct ActArgs {
@@ -1796,6 +1592,49 @@ struct ActArgs {
     float *q_out;          // nullable [n][A]
     const float *img;      // nullable: q_local's layer 1 in the split form (packed rows, f32 MFMA)
 };
+
+// fc2 / b2 of an acting workgroup of 256 threads: requested with the other weights, committed to W2 [16][64] / b2 [16] behind them
+struct Fc2Regs {
+    float pw[4], pb2;
+};
+__device__ __forceinline__ void fc2_issue(Fc2Regs &v, const NetDev &nl, int n2)
+{
+    const int tid = (int)threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v.pw[k] = nl.W2[tid + 256 * k < n2 * kHid ? tid + 256 * k : 0];
+    v.pb2 = nl.b2[tid < n2 ? tid : 0];
+}
+__device__ __forceinline__ void fc2_commit(float *W2, float *b2, const Fc2Regs &v, int n2)
+{
+    const int tid = (int)threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (tid + 256 * k < n2 * kHid) W2[tid + 256 * k] = v.pw[k];
+    if (tid < n2) b2[tid] = v.pb2;
+}
+
+// What an acting lane leaves for agent i: its Q row (q_out nullable), then the epsilon-greedy action (policy_select_n on rn, the
+// policy_philox draw of the lane's env) as an index and as a steer in [-1, 1] (each nullable)
+template <int NMAX>
+__device__ __forceinline__ void act_q_store(float *q_out, size_t i, int n_actions, const float (&q)[NMAX])
+{
+    if (!q_out) return;
+#pragma unroll
+    for (int a = 0; a < NMAX; ++a)
+        if (a < n_actions) q_out[i * n_actions + a] = q[a];
+}
+__device__ __forceinline__ void act_action_store(int32_t *index_out, float *steer_out, size_t i, int a, int n_actions)
+{
+    if (index_out) index_out[i] = a;
+    if (steer_out) steer_out[i] = (float)(-1.0 + 2.0 * (double)a / (double)(n_actions - 1));
+}
+template <int NMAX>
+__device__ __forceinline__ void act_finish(const float (&q)[NMAX], uint4 rn, float eps, int n_actions, size_t i, int32_t *index_out,
+                                           float *steer_out, float *q_out)
+{
+    act_q_store<NMAX>(q_out, i, n_actions, q);
+    act_action_store(index_out, steer_out, i, policy_select_n<NMAX>(q, rn, eps, n_actions), n_actions);
+}
 
 // Q(s) + epsilon-greedy for a tile of 64 envs (Trainer/DuelingDQN_Trainer.py:86-97), same wave-strip forward as
 // k_dqn_grad: wavefront w owns rows 16 w .. 16 w + 15 of the tile (consecutive observation rows: one 6.4 KB run).
@@ -1829,19 +1668,13 @@ __global__ void __launch_bounds__(256) k_dqn_act(ActArgs g)
     w_issue(vW, g.local);
     // the epsilon-greedy draw of this lane's env: a serial chain, computed under the loads' round trip
     const int i = first + r;
-    const uint4 rn = philox4x32_10(make_uint4((uint32_t)i, (uint32_t)g.counter, (uint32_t)(g.counter >> 32), 0xac7u),
-                                   make_uint2((uint32_t)g.seed, (uint32_t)(g.seed >> 32)));
+    const uint4 rn = policy_philox(i, g.seed, g.counter);
     const float pb1 = nl.b1[tid < kHid ? tid : kHid - 1];
-    float pw[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pw[k] = nl.W2[tid + 256 * k < n2 * kHid ? tid + 256 * k : 0];
-    const float pb2 = nl.b2[tid < n2 ? tid : 0];
+    Fc2Regs v2;
+    fc2_issue(v2, nl, n2);
     x_commit<ObsT>(strip, vX);
     w_commit(W1, vW, pb1);
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (tid + 256 * k < n2 * kHid) W2[tid + 256 * k] = pw[k];
-    if (tid < n2) b2[tid] = pb2;
+    fc2_commit(W2, b2, v2, n2);
     __syncthreads();
     floatx4 h[4];
     fwd_strip(W1, strip, h);
@@ -1851,58 +1684,37 @@ __global__ void __launch_bounds__(256) k_dqn_act(ActArgs g)
         w2_load<NMAX>(F, W2, b2, n2);
         q_strip<NMAX>(h, F, n2, g.n_actions, g.dueling, q);
     }
-    if (lane < 16 && i < g.n) {
-        if (g.q_out) {
-#pragma unroll
-            for (int a = 0; a < NMAX; ++a)
-                if (a < g.n_actions) g.q_out[(size_t)i * g.n_actions + a] = q[a];
-        }
-        const float sample = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
-        int a;
-        if (sample > g.eps) {
-            a = 0;
-            float bq = q[0];
-#pragma unroll
-            for (int k = 1; k < NMAX; ++k)
-                if (k < g.n_actions && q[k] > bq) { bq = q[k]; a = k; }
-        } else {
-            a = (int)(((uint64_t)rn.y * (uint64_t)g.n_actions) >> 32);
-        }
-        if (g.index_out) g.index_out[i] = a;
-        if (g.steer_out) g.steer_out[i] = (float)(-1.0 + 2.0 * (double)a / (double)(g.n_actions - 1));
-    }
+    if (lane < 16 && i < g.n) act_finish<NMAX>(q, rn, g.eps, g.n_actions, (size_t)i, g.index_out, g.steer_out, g.q_out);
 }
 
 // Packed observations: no observation tile -- every lane loads the packed row of its env and generates the MFMA operands
 // from it (fwd_strip_split, qnet_device.hpp "Layer 1 at f32 accuracy on the f16 matrix pipe"); LDS holds the weights only.
+// The one body of k_dqn_act_packed and k_dqn_act_slots: the lane's env e (of n) reads packed row e * U + j and writes agent
+// e * U + j, with net `local` (+ its layer-1 image, nullable) and the draw of env e under `seed`.  k_dqn_act_packed: U = 1, j = 0.
 template <int NMAX>
-__global__ void __launch_bounds__(256) k_dqn_act_packed(ActArgs g)
+__device__ __forceinline__ void act_packed_body(const void *obs, int n, int U, int j, const float *local, const float *img,
+                                                int n_actions, int dueling, float eps, uint64_t seed, uint64_t counter,
+                                                int32_t *index_out, float *steer_out, float *q_out)
 {
     extern __shared__ __align__(16) float lds[];
     const W1Split W1 = w1split_at(lds);     // fc1 + b1 in the split form (kTileF floats)
     float *W2 = lds + kSplitF;              // [16][64]
     float *b2 = W2 + kMaxOut * kHid;        // [16]
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 15;
-    const int n2 = g.n_actions + (g.dueling ? 1 : 0);
-    const NetDev nl = net_view(g.local, n2);
-    const int i = (int)blockIdx.x * kTile + wv * 16 + r;
+    const int n2 = n_actions + (dueling ? 1 : 0);
+    const NetDev nl = net_view(local, n2);
+    const int e = (int)blockIdx.x * kTile + wv * 16 + r;
     floatx4 vW[kStageIters];
     SplitScRegs vS;
-    if (g.img) img_issue(vW, g.img); else { w_issue(vW, g.local); w_issue_sc(vS, g.local, nl.b1); }
-    float pw[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pw[k] = nl.W2[tid + 256 * k < n2 * kHid ? tid + 256 * k : 0];
-    const float pb2 = nl.b2[tid < n2 ? tid : 0];
+    if (img) img_issue(vW, img); else { w_issue(vW, local); w_issue_sc(vS, local, nl.b1); }
+    Fc2Regs v2;
+    fc2_issue(v2, nl, n2);
     PRow R;
-    prow_load(R, reinterpret_cast<const uint32_t *>(g.obs) + (size_t)(i < g.n ? i : g.n - 1) * kPackedDwords);
+    prow_load(R, reinterpret_cast<const uint32_t *>(obs) + ((size_t)(e < n ? e : n - 1) * (size_t)U + (size_t)j) * kPackedDwords);
     // the epsilon-greedy draw of this lane's env: a serial chain, computed under the loads' round trip
-    const uint4 rn = philox4x32_10(make_uint4((uint32_t)i, (uint32_t)g.counter, (uint32_t)(g.counter >> 32), 0xac7u),
-                                   make_uint2((uint32_t)g.seed, (uint32_t)(g.seed >> 32)));
-    if (g.img) img_commit(lds, vW); else w_commit_split(W1, vW, vS);
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (tid + 256 * k < n2 * kHid) W2[tid + 256 * k] = pw[k];
-    if (tid < n2) b2[tid] = pb2;
+    const uint4 rn = policy_philox(e, seed, counter);
+    if (img) img_commit(lds, vW); else w_commit_split(W1, vW, vS);
+    fc2_commit(W2, b2, v2, n2);
     __syncthreads();
     floatx4 h[4];
     fwd_strip_split<false>(W1, R, h);
@@ -1910,34 +1722,22 @@ __global__ void __launch_bounds__(256) k_dqn_act_packed(ActArgs g)
     {
         W2Frag<NMAX> F;
         w2_load<NMAX>(F, W2, b2, n2);
-        q_strip<NMAX>(h, F, n2, g.n_actions, g.dueling, q);
+        q_strip<NMAX>(h, F, n2, n_actions, dueling, q);
     }
-    if (lane < 16 && i < g.n) {
-        if (g.q_out) {
-#pragma unroll
-            for (int a = 0; a < NMAX; ++a)
-                if (a < g.n_actions) g.q_out[(size_t)i * g.n_actions + a] = q[a];
-        }
-        const float sample = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
-        int a;
-        if (sample > g.eps) {
-            a = 0;
-            float bq = q[0];
-#pragma unroll
-            for (int k = 1; k < NMAX; ++k)
-                if (k < g.n_actions && q[k] > bq) { bq = q[k]; a = k; }
-        } else {
-            a = (int)(((uint64_t)rn.y * (uint64_t)g.n_actions) >> 32);
-        }
-        if (g.index_out) g.index_out[i] = a;
-        if (g.steer_out) g.steer_out[i] = (float)(-1.0 + 2.0 * (double)a / (double)(g.n_actions - 1));
-    }
+    if (lane < 16 && e < n)
+        act_finish<NMAX>(q, rn, eps, n_actions, (size_t)e * (size_t)U + (size_t)j, index_out, steer_out, q_out);
 }
 
-// One net per UAV slot on the packed rows of one frame (agent = env * U + slot): k_dqn_act_packed's body, where slice blockIdx.y of
-// the grid stages net y and a lane's env e reads packed row e * U + y.  Same device functions in the same order, so the Q row and
-// the action of agent e * U + y are bit for bit those of k_dqn_act_packed with net y on slot y's rows gathered contiguously, under
-// the key seed + y (the draw is keyed by the env, as there).
+template <int NMAX>
+__global__ void __launch_bounds__(256) k_dqn_act_packed(ActArgs g)
+{
+    act_packed_body<NMAX>(g.obs, g.n, 1, 0, g.local, g.img, g.n_actions, g.dueling, g.eps, g.seed, g.counter, g.index_out,
+                          g.steer_out, g.q_out);
+}
+
+// One net per UAV slot on the packed rows of one frame (agent = env * U + slot): slice blockIdx.y of the grid stages net y and a
+// lane's env e reads packed row e * U + y.  The same body, so the Q row and the action of agent e * U + y are bit for bit those of
+// k_dqn_act_packed with net y on slot y's rows gathered contiguously, under the key seed + y (the draw is keyed by the env, as there).
 struct ActSlotsArgs {
     const void *obs;       // [n_envs * n_nets][20 dwords]
     int n_envs, n_nets, n_actions, dueling;
@@ -1951,64 +1751,9 @@ struct ActSlotsArgs {
 template <int NMAX>
 __global__ void __launch_bounds__(256) k_dqn_act_slots(ActSlotsArgs g)
 {
-    extern __shared__ __align__(16) float lds[];
-    const W1Split W1 = w1split_at(lds);     // fc1 + b1 in the split form (kTileF floats)
-    float *W2 = lds + kSplitF;              // [16][64]
-    float *b2 = W2 + kMaxOut * kHid;        // [16]
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 15;
     const int j = (int)blockIdx.y;
-    const float *local = g.net[j].local, *img = g.net[j].img;
-    const uint64_t seed = g.seed + (uint64_t)j;
-    const int n2 = g.n_actions + (g.dueling ? 1 : 0);
-    const NetDev nl = net_view(local, n2);
-    const int e = (int)blockIdx.x * kTile + wv * 16 + r;
-    floatx4 vW[kStageIters];
-    SplitScRegs vS;
-    if (img) img_issue(vW, img); else { w_issue(vW, local); w_issue_sc(vS, local, nl.b1); }
-    float pw[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pw[k] = nl.W2[tid + 256 * k < n2 * kHid ? tid + 256 * k : 0];
-    const float pb2 = nl.b2[tid < n2 ? tid : 0];
-    PRow R;
-    prow_load(R, reinterpret_cast<const uint32_t *>(g.obs) +
-                     ((size_t)(e < g.n_envs ? e : g.n_envs - 1) * (size_t)g.n_nets + (size_t)j) * kPackedDwords);
-    // the epsilon-greedy draw of this lane's env: a serial chain, computed under the loads' round trip
-    const uint4 rn = philox4x32_10(make_uint4((uint32_t)e, (uint32_t)g.counter, (uint32_t)(g.counter >> 32), 0xac7u),
-                                   make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-    if (img) img_commit(lds, vW); else w_commit_split(W1, vW, vS);
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (tid + 256 * k < n2 * kHid) W2[tid + 256 * k] = pw[k];
-    if (tid < n2) b2[tid] = pb2;
-    __syncthreads();
-    floatx4 h[4];
-    fwd_strip_split<false>(W1, R, h);
-    float q[NMAX];
-    {
-        W2Frag<NMAX> F;
-        w2_load<NMAX>(F, W2, b2, n2);
-        q_strip<NMAX>(h, F, n2, g.n_actions, g.dueling, q);
-    }
-    if (lane < 16 && e < g.n_envs) {
-        const size_t i = (size_t)e * (size_t)g.n_nets + (size_t)j;
-        if (g.q_out) {
-#pragma unroll
-            for (int a = 0; a < NMAX; ++a)
-                if (a < g.n_actions) g.q_out[i * g.n_actions + a] = q[a];
-        }
-        const float sample = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
-        int a;
-        if (sample > g.eps) {
-            a = 0;
-            float bq = q[0];
-#pragma unroll
-            for (int k = 1; k < NMAX; ++k)
-                if (k < g.n_actions && q[k] > bq) { bq = q[k]; a = k; }
-        } else {
-            a = (int)(((uint64_t)rn.y * (uint64_t)g.n_actions) >> 32);
-        }
-        g.index_out[i] = a;
-    }
+    act_packed_body<NMAX>(g.obs, g.n_envs, g.n_nets, j, g.net[j].local, g.net[j].img, g.n_actions, g.dueling, g.eps,
+                          g.seed + (uint64_t)j, g.counter, g.index_out, nullptr, g.q_out);
 }
 
 // f16 MFMA forward (UavDqnNet.mfma_dtype = 1) on f16 or packed observations.  Workgroups are persistent over tiles (the
@@ -2056,15 +1801,10 @@ __global__ void __launch_bounds__(256) k_dqn_act_h(ActArgs g)
         floatx4 vW[kStageIters];
         w_issue(vW, g.local);
         const float pb1 = nl.b1[tid < kHid ? tid : kHid - 1];
-        float pw[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) pw[k] = nl.W2[tid + 256 * k < n2 * kHid ? tid + 256 * k : 0];
-        const float pb2 = nl.b2[tid < n2 ? tid : 0];
+        Fc2Regs v2;
+        fc2_issue(v2, nl, n2);
         wh_commit(W1, vW, pb1);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (tid + 256 * k < n2 * kHid) W2[tid + 256 * k] = pw[k];
-        if (tid < n2) b2[tid] = pb2;
+        fc2_commit(W2, b2, v2, n2);
     }
     __syncthreads();
     W2Frag<NMAX> F;
@@ -2074,32 +1814,12 @@ __global__ void __launch_bounds__(256) k_dqn_act_h(ActArgs g)
         xh_commit<KIND>(strip, vX, stage + wv * kStageW, nullptr);
         wave_lds_sync();
         if (tile + (int)gridDim.x < n_tiles) act_rows_issue<KIND>(g, (tile + (int)gridDim.x) * kTile + wv * 16, vX);
-        const uint4 rn = philox4x32_10(make_uint4((uint32_t)i, (uint32_t)g.counter, (uint32_t)(g.counter >> 32), 0xac7u),
-                                       make_uint2((uint32_t)g.seed, (uint32_t)(g.seed >> 32)));
+        const uint4 rn = policy_philox(i, g.seed, g.counter);
         floatx4 h[4];
         fwd_strip_h(W1, strip, h);
         float q[NMAX];
         q_strip<NMAX, 3>(h, F, n2, g.n_actions, g.dueling, q);
-        if (lane < 16 && i < g.n) {
-            if (g.q_out) {
-#pragma unroll
-                for (int a = 0; a < NMAX; ++a)
-                    if (a < g.n_actions) g.q_out[(size_t)i * g.n_actions + a] = q[a];
-            }
-            const float sample = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
-            int a;
-            if (sample > g.eps) {
-                a = 0;
-                float bq = q[0];
-#pragma unroll
-                for (int k = 1; k < NMAX; ++k)
-                    if (k < g.n_actions && q[k] > bq) { bq = q[k]; a = k; }
-            } else {
-                a = (int)(((uint64_t)rn.y * (uint64_t)g.n_actions) >> 32);
-            }
-            if (g.index_out) g.index_out[i] = a;
-            if (g.steer_out) g.steer_out[i] = (float)(-1.0 + 2.0 * (double)a / (double)(g.n_actions - 1));
-        }
+        if (lane < 16 && i < g.n) act_finish<NMAX>(q, rn, g.eps, g.n_actions, (size_t)i, g.index_out, g.steer_out, g.q_out);
         wave_lds_sync();                      // the strip is rewritten by the next tile's commit
     }
 }
@@ -2116,110 +1836,75 @@ bool net_ok(const UavDqnNet *n)
            n->n_actions + (n->dueling ? 1 : 0) + 2 <= kMaxOut;     // + 2 spare dout columns (loss sum, valid count)
 }
 
-template <int KIND>
-static int launch_grad_h8(const Grad2Args &ga, int grid, hipStream_t s)
+bool al16(const void *a, const void *b = nullptr, const void *c = nullptr, const void *d = nullptr)
 {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_h8<KIND>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradH8Lds) != hipSuccess)
-            return UAVENV_EHIP;
-        attr = true;
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15u) == 0;
+}
+
+// The one launcher of this file: `lds` bytes of dynamic LDS; above the 64 KB default the kernel's
+// hipFuncAttributeMaxDynamicSharedMemorySize is raised first, once per kernel (every kernel here has one LDS size).
+template <auto Kernel, typename Args>
+int launch(dim3 grid, int block, size_t lds, hipStream_t s, const Args &a)
+{
+    if (lds > 65536) {
+        static bool attr = false;
+        if (!attr) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+                return UAVENV_EHIP;
+            attr = true;
+        }
     }
-    hipLaunchKernelGGL((k_dqn_grad_h8<KIND>), dim3(grid), dim3(512), kGradH8Lds, s, ga);
-    return UAVENV_OK;
+    hipLaunchKernelGGL(Kernel, grid, dim3(block), lds, s, a);
+    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
 }
 
-template <int KIND>
-static int launch_act_h(const ActArgs &g, int grid, hipStream_t s)
+// with a layer-1 image the packed8 family stages both images by LDS-DMA; UAVENV_STAGE_VGPR=1 keeps the register-staged form, the
+// reference that the DMA staging is held to bit for bit
+bool stage_vgpr()
 {
-    hipLaunchKernelGGL((k_dqn_act_h<KIND, 4>), dim3(grid < 512 ? grid : 512), dim3(256), kActHLds, s, g);   // 44 KB: no attribute needed
-    return UAVENV_OK;
+    static const bool on = getenv("UAVENV_STAGE_VGPR") && atoi(getenv("UAVENV_STAGE_VGPR")) != 0;
+    return on;
 }
 
-template <int NMAX>
-static int launch_act_packed(const ActArgs &g, int grid, hipStream_t s)
+// the ring, head and batch of a gradient call
+bool grad_ring_ok(const UavReplayRing *ring, int32_t head, int32_t batch)
 {
-    hipLaunchKernelGGL((k_dqn_act_packed<NMAX>), dim3(grid), dim3(256), kActPLds, s, g);      // 32 KB: no attribute needed
-    return UAVENV_OK;
+    return ring && ring->obs && ring->action && ring->reward && ring->done && batch > 0 && batch % kTile == 0 && ring->frames >= 2 &&
+           head >= 0 && head < ring->frames && (uint64_t)ring->frames * (uint64_t)ring->n_agents < (1ull << 32) &&
+           ring->action_is_index && al16(ring->meta);
 }
 
-template <int NMAX>
-static int launch_act_slots(const ActSlotsArgs &g, int grid, hipStream_t s)
+// what a gradient launch takes from the ring, the draw and the head of `net`; the caller adds the nets' pointers and the nullable extras
+void grad_args_fill(Grad2Args &ga, const UavReplayRing *ring, int32_t head, int32_t filled, int32_t batch, uint64_t seed, uint64_t counter,
+                    const int32_t *explicit_idx, const UavDqnNet *net, int32_t kind, float gamma, int32_t huber)
 {
-    hipLaunchKernelGGL((k_dqn_act_slots<NMAX>), dim3(grid, g.n_nets), dim3(256), kActPLds, s, g);   // 32 KB: no attribute needed
-    return UAVENV_OK;
+    GradArgs &g = ga.g;
+    g.ring = *ring;
+    g.head = head; g.filled = filled; g.batch = batch;
+    g.seed = seed; g.counter = counter;
+    g.explicit_idx = explicit_idx;
+    g.perm = replay_perm(seed, counter, explicit_idx ? 1u : (uint32_t)filled * (uint32_t)ring->n_agents, (uint32_t)ring->n_agents);
+    g.local = nullptr; g.target = nullptr; g.partials = nullptr; g.img = nullptr;
+    g.n_actions = net->n_actions; g.dueling = net->dueling; g.kind = kind;
+    g.gamma = gamma; g.huber = huber;
+    g.P = uavenv_dqn_num_params(net);
+    g.dbg = nullptr; g.is_w = nullptr; g.abs_td = nullptr;
+    ga.n_tiles = batch / kTile;
+    ga.stride = uavenv_dqn_partial_stride(net);
 }
 
-template <typename ObsT, int NMAX>
-static int launch_act(const ActArgs &g, int grid, hipStream_t s)
+// slot j of a per-slot call: a usable net with the head of net 0 and, where the call has partial rows, 16-byte aligned rows and a
+// net of its own (no earlier slot's)
+bool slot_ok(const UavDqnNet *const *nets, float *const *partials, int j)
 {
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_act<ObsT, NMAX>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAct2Lds) != hipSuccess)
-            return UAVENV_EHIP;
-        attr = true;
-    }
-    hipLaunchKernelGGL((k_dqn_act<ObsT, NMAX>), dim3(grid), dim3(256), kAct2Lds, s, g);
-    return UAVENV_OK;
+    const UavDqnNet *n = nets[j];
+    if (!net_ok(n) || n->n_actions != nets[0]->n_actions || (n->dueling != 0) != (nets[0]->dueling != 0)) return false;
+    if (!partials) return true;
+    if (!partials[j] || !al16(partials[j])) return false;
+    for (int i = 0; i < j; ++i)
+        if (nets[i]->local == n->local || partials[i] == partials[j]) return false;
+    return true;
 }
-
-static int launch_grad_packed(const Grad2Args &ga, int grid, hipStream_t s)       // packed rows, more than 4 layer-2 outputs
-{
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed<kMaxOut - 2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradPLds) != hipSuccess)
-            return UAVENV_EHIP;
-        attr = true;
-    }
-    hipLaunchKernelGGL((k_dqn_grad_packed<kMaxOut - 2>), dim3(grid), dim3(256), kGradPLds, s, ga);
-    return UAVENV_OK;
-}
-
-template <bool GLDS>
-static int launch_grad_packed8(const Grad2Args &ga, int grid, hipStream_t s)
-{
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_packed8<GLDS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess)
-            return UAVENV_EHIP;
-        attr = true;
-    }
-    hipLaunchKernelGGL((k_dqn_grad_packed8<GLDS>), dim3(grid), dim3(512), kGradP8Lds, s, ga);
-    return UAVENV_OK;
-}
-
-template <bool GLDS>
-static int launch_grad_slots(const GradSlotsArgs &sa, int grid, int n_nets, hipStream_t s)
-{
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad_slots<GLDS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradP8Lds) != hipSuccess)
-            return UAVENV_EHIP;
-        attr = true;
-    }
-    hipLaunchKernelGGL((k_dqn_grad_slots<GLDS>), dim3(grid, n_nets), dim3(512), kGradP8Lds, s, sa);
-    return UAVENV_OK;
-}
-
-template <typename ObsT, int NMAX>
-static int launch_grad(const Grad2Args &ga, int grid, hipStream_t s)
-{
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dqn_grad<ObsT, NMAX>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGrad2Lds) != hipSuccess)
-            return UAVENV_EHIP;
-        attr = true;
-    }
-    hipLaunchKernelGGL((k_dqn_grad<ObsT, NMAX>), dim3(grid), dim3(256), kGrad2Lds, s, ga);
-    return UAVENV_OK;
-}
-
 
 }  // namespace
 
@@ -2275,51 +1960,33 @@ int uavenv_dqn_grad_img(const UavReplayRing *ring, int32_t head, int32_t filled,
                         uint64_t counter, const int32_t *explicit_idx, const UavDqnNet *net, int32_t kind, float gamma,
                         int32_t huber, const float *is_weights, float *abs_td_out, float *partials, const float *image_dev, void *stream)
 {
-    if (!ring || !ring->obs || !ring->action || !ring->reward || !ring->done || !partials || !net_ok(net) || !net->target)
-        return UAVENV_EINVAL;
-    if (batch <= 0 || batch % kTile != 0 || ring->frames < 2 || head < 0 || head >= ring->frames) return UAVENV_EINVAL;
+    if (!grad_ring_ok(ring, head, batch) || !partials || !net_ok(net) || !net->target) return UAVENV_EINVAL;
     if (!explicit_idx && (filled <= 0 || filled > ring->frames - 1)) return UAVENV_EINVAL;
-    if ((uint64_t)ring->frames * (uint64_t)ring->n_agents >= (1ull << 32)) return UAVENV_EINVAL;
-    if (!ring->action_is_index) return UAVENV_EINVAL;
-    if ((((uintptr_t)partials | (uintptr_t)net->local | (uintptr_t)net->target | (uintptr_t)ring->meta) & 15u) != 0) return UAVENV_EINVAL;
+    if (!al16(partials, net->local, net->target)) return UAVENV_EINVAL;
     Grad2Args ga;
+    grad_args_fill(ga, ring, head, filled, batch, seed, counter, explicit_idx, net, kind, gamma, huber);
     GradArgs &g = ga.g;
-    g.ring = *ring;
-    g.head = head; g.filled = filled; g.batch = batch;
-    g.seed = seed; g.counter = counter;
-    g.explicit_idx = explicit_idx;
-    g.perm = replay_perm(seed, counter, explicit_idx ? 1u : (uint32_t)filled * (uint32_t)ring->n_agents, (uint32_t)ring->n_agents);
     g.local = net->local; g.target = net->target;
-    g.n_actions = net->n_actions; g.dueling = net->dueling; g.kind = kind;
-    g.gamma = gamma; g.huber = huber;
     g.partials = partials;
-    g.P = uavenv_dqn_num_params(net);
     g.dbg = g_learner_dbg;
     g.is_w = is_weights;
     g.abs_td = abs_td_out;
-    g.img = (image_dev && (((uintptr_t)image_dev) & 15u) == 0) ? image_dev : nullptr;
-    ga.n_tiles = batch / kTile;
-    ga.stride = uavenv_dqn_partial_stride(net);
-    const int grid = uavenv_dqn_partial_rows(batch);
+    g.img = (image_dev && al16(image_dev)) ? image_dev : nullptr;
+    const dim3 grid(uavenv_dqn_partial_rows(batch));
     hipStream_t s = (hipStream_t)stream;
     const bool small = net->n_actions + (net->dueling ? 1 : 0) <= 4;
-    int rc;
     if (net->mfma_dtype == UAVENV_MFMA_F16) {         // f16 operands, f32 accumulate: f16 / packed rings, <= 4 layer-2 outputs
         if (!small || ring->obs_dtype == UAVENV_OBS_F32) return UAVENV_EINVAL;
-        rc = ring->obs_dtype == UAVENV_OBS_PACKED ? launch_grad_h8<OBS_KIND_PACKED>(ga, grid, s) : launch_grad_h8<OBS_KIND_F16>(ga, grid, s);
-    } else if (ring->obs_dtype == UAVENV_OBS_F32)
-        rc = small ? launch_grad<float, 4>(ga, grid, s) : launch_grad<float, kMaxOut - 2>(ga, grid, s);
-    else if (ring->obs_dtype != UAVENV_OBS_PACKED)
-        rc = small ? launch_grad<__half, 4>(ga, grid, s) : launch_grad<__half, kMaxOut - 2>(ga, grid, s);
-    else if (small) {
-        // with a layer-1 image both images are staged by LDS-DMA; UAVENV_STAGE_VGPR=1 keeps the register-staged form, the reference
-        // that the DMA staging is held to bit for bit
-        static const bool stage_vgpr = getenv("UAVENV_STAGE_VGPR") && atoi(getenv("UAVENV_STAGE_VGPR")) != 0;
-        rc = g.img && !stage_vgpr ? launch_grad_packed8<true>(ga, grid, s) : launch_grad_packed8<false>(ga, grid, s);
-    } else
-        rc = launch_grad_packed(ga, grid, s);
-    if (rc != UAVENV_OK) return rc;
-    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+        return ring->obs_dtype == UAVENV_OBS_PACKED ? launch<k_dqn_grad_h8<OBS_KIND_PACKED>>(grid, 512, kGradH8Lds, s, ga)
+                                                    : launch<k_dqn_grad_h8<OBS_KIND_F16>>(grid, 512, kGradH8Lds, s, ga);
+    }
+    if (ring->obs_dtype == UAVENV_OBS_F32)
+        return small ? launch<k_dqn_grad<float, 4>>(grid, 256, kGrad2Lds, s, ga) : launch<k_dqn_grad<float, kMaxOut - 2>>(grid, 256, kGrad2Lds, s, ga);
+    if (ring->obs_dtype != UAVENV_OBS_PACKED)
+        return small ? launch<k_dqn_grad<__half, 4>>(grid, 256, kGrad2Lds, s, ga) : launch<k_dqn_grad<__half, kMaxOut - 2>>(grid, 256, kGrad2Lds, s, ga);
+    if (!small) return launch<k_dqn_grad_packed<kMaxOut - 2>>(grid, 256, kGradPLds, s, ga);     // packed rows, more than 4 layer-2 outputs
+    return g.img && !stage_vgpr() ? launch<k_dqn_grad_packed8<true>>(grid, 512, kGradP8Lds, s, ga)
+                                  : launch<k_dqn_grad_packed8<false>>(grid, 512, kGradP8Lds, s, ga);
 }
 
 int uavenv_dqn_reduce(const UavDqnNet *net, const float *partials, int32_t n_partials, float *raw_out, void *stream)
@@ -2414,19 +2081,21 @@ int uavenv_dqn_act(const UavDqnNet *net, const void *obs_dev, int32_t obs_dtype,
     g.local = net->local; g.eps = eps; g.seed = seed; g.counter = counter;
     g.index_out = index_out; g.steer_out = steer_out; g.q_out = q_out;
     g.img = nullptr;
-    const int grid = (n + kTile - 1) / kTile;
+    const int tiles = (n + kTile - 1) / kTile;
+    const dim3 grid(tiles);
     hipStream_t s = (hipStream_t)stream;
     const bool small = net->n_actions + (net->dueling ? 1 : 0) <= 4;
-    int rc;
-    if (net->mfma_dtype == UAVENV_MFMA_F16) {
+    if (net->mfma_dtype == UAVENV_MFMA_F16) {         // persistent workgroups, 44 KB
         if (!small || obs_dtype == UAVENV_OBS_F32) return UAVENV_EINVAL;
-        rc = obs_dtype == UAVENV_OBS_PACKED ? launch_act_h<OBS_KIND_PACKED>(g, grid, s) : launch_act_h<OBS_KIND_F16>(g, grid, s);
-    } else if (obs_dtype == UAVENV_OBS_F32) rc = small ? launch_act<float, 4>(g, grid, s) : launch_act<float, kMaxOut - 2>(g, grid, s);
-    else if (obs_dtype == UAVENV_OBS_PACKED)
-        rc = small ? launch_act_packed<4>(g, grid, s) : launch_act_packed<kMaxOut - 2>(g, grid, s);
-    else rc = small ? launch_act<__half, 4>(g, grid, s) : launch_act<__half, kMaxOut - 2>(g, grid, s);
-    if (rc != UAVENV_OK) return rc;
-    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+        const dim3 gh(tiles < 512 ? tiles : 512);
+        return obs_dtype == UAVENV_OBS_PACKED ? launch<k_dqn_act_h<OBS_KIND_PACKED, 4>>(gh, 256, kActHLds, s, g)
+                                              : launch<k_dqn_act_h<OBS_KIND_F16, 4>>(gh, 256, kActHLds, s, g);
+    }
+    if (obs_dtype == UAVENV_OBS_F32)
+        return small ? launch<k_dqn_act<float, 4>>(grid, 256, kAct2Lds, s, g) : launch<k_dqn_act<float, kMaxOut - 2>>(grid, 256, kAct2Lds, s, g);
+    if (obs_dtype == UAVENV_OBS_PACKED)
+        return small ? launch<k_dqn_act_packed<4>>(grid, 256, kActPLds, s, g) : launch<k_dqn_act_packed<kMaxOut - 2>>(grid, 256, kActPLds, s, g);
+    return small ? launch<k_dqn_act<__half, 4>>(grid, 256, kAct2Lds, s, g) : launch<k_dqn_act<__half, kMaxOut - 2>>(grid, 256, kAct2Lds, s, g);
 }
 
 // (internal, csrc/dqn_slots_internal.hpp) images: n_nets pointers (host array, nullable as a whole and per net) to uavenv_dqn_split_image's
@@ -2443,8 +2112,7 @@ int uavenv_dqn_act_slots_img(const UavDqnNet *const *nets, int32_t n_nets, const
     for (int j = 0; j < kActMaxSlots; ++j) { g.net[j].local = nullptr; g.net[j].img = nullptr; }
     for (int j = 0; j < n_nets; ++j) {
         const UavDqnNet *n = nets[j];
-        if (!net_ok(n) || n->mfma_dtype != UAVENV_MFMA_F32 || (((uintptr_t)n->local) & 15u) != 0) return UAVENV_EINVAL;
-        if (n->n_actions != nets[0]->n_actions || (n->dueling != 0) != (nets[0]->dueling != 0)) return UAVENV_EINVAL;
+        if (!slot_ok(nets, nullptr, j) || n->mfma_dtype != UAVENV_MFMA_F32 || !al16(n->local)) return UAVENV_EINVAL;
         g.net[j].local = n->local;
         if (images && images[j]) {
             if ((((uintptr_t)images[j]) & 15u) != 0) return UAVENV_EINVAL;
@@ -2454,11 +2122,9 @@ int uavenv_dqn_act_slots_img(const UavDqnNet *const *nets, int32_t n_nets, const
     g.obs = obs_dev; g.n_envs = n_envs; g.n_nets = n_nets; g.n_actions = nets[0]->n_actions; g.dueling = nets[0]->dueling ? 1 : 0;
     g.eps = eps; g.seed = seed; g.counter = counter;
     g.index_out = index_out; g.q_out = q_out;
-    const int grid = (n_envs + kTile - 1) / kTile;
-    const bool small = g.n_actions + g.dueling <= 4;
-    const int rc = small ? launch_act_slots<4>(g, grid, (hipStream_t)stream) : launch_act_slots<kMaxOut - 2>(g, grid, (hipStream_t)stream);
-    if (rc != UAVENV_OK) return rc;
-    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+    const dim3 grid((n_envs + kTile - 1) / kTile, n_nets);
+    return g.n_actions + g.dueling <= 4 ? launch<k_dqn_act_slots<4>>(grid, 256, kActPLds, (hipStream_t)stream, g)
+                                        : launch<k_dqn_act_slots<kMaxOut - 2>>(grid, 256, kActPLds, (hipStream_t)stream, g);
 }
 
 int uavenv_dqn_act_slots(const UavDqnNet *const *nets, int32_t n_nets, const void *obs_dev, int32_t obs_dtype, int32_t n_envs,
@@ -2475,52 +2141,28 @@ int uavenv_dqn_grad_slots_img(const UavReplayRing *ring, int32_t head, int32_t f
                               int32_t huber, float *const *partials, const float *const *images, void *stream)
 {
     if (!nets || !partials || !pairs_dev || n_nets < 1 || n_nets > kActMaxSlots) return UAVENV_EINVAL;
-    if (!ring || !ring->obs || !ring->action || !ring->reward || !ring->done || ring->obs_dtype != UAVENV_OBS_PACKED) return UAVENV_EINVAL;
-    if (batch <= 0 || batch % kTile != 0 || ring->frames < 2 || head < 0 || head >= ring->frames) return UAVENV_EINVAL;
-    if ((uint64_t)ring->frames * (uint64_t)ring->n_agents >= (1ull << 32) || !ring->action_is_index) return UAVENV_EINVAL;
-    if ((((uintptr_t)ring->meta) & 15u) != 0 || (((uintptr_t)pairs_dev) & 7u) != 0) return UAVENV_EINVAL;
+    if (!grad_ring_ok(ring, head, batch) || ring->obs_dtype != UAVENV_OBS_PACKED || (((uintptr_t)pairs_dev) & 7u) != 0) return UAVENV_EINVAL;
     GradSlotsArgs sa;
     bool all_img = true;
     for (int j = 0; j < kActMaxSlots; ++j) sa.slot[j] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     for (int j = 0; j < n_nets; ++j) {
         const UavDqnNet *n = nets[j];
-        if (!net_ok(n) || !n->target || !partials[j] || n->mfma_dtype != UAVENV_MFMA_F32) return UAVENV_EINVAL;
+        if (!slot_ok(nets, partials, j) || !n->target || n->mfma_dtype != UAVENV_MFMA_F32 || !al16(n->local, n->target)) return UAVENV_EINVAL;
         if (n->n_actions + (n->dueling ? 1 : 0) > 4) return UAVENV_EINVAL;                       // the packed8 family only
-        if (n->n_actions != nets[0]->n_actions || (n->dueling != 0) != (nets[0]->dueling != 0)) return UAVENV_EINVAL;
-        if ((((uintptr_t)partials[j] | (uintptr_t)n->local | (uintptr_t)n->target) & 15u) != 0) return UAVENV_EINVAL;
-        for (int i = 0; i < j; ++i)
-            if (nets[i]->local == n->local || partials[i] == partials[j]) return UAVENV_EINVAL;
         const float *im = images ? images[j] : nullptr;
         sa.slot[j].local = n->local;
         sa.slot[j].target = n->target;
-        sa.slot[j].img = (im && (((uintptr_t)im) & 15u) == 0) ? im : nullptr;       // (as uavenv_dqn_grad_img: such a net converts for itself)
+        sa.slot[j].img = (im && al16(im)) ? im : nullptr;       // (as uavenv_dqn_grad_img: such a net converts for itself)
         sa.slot[j].partials = partials[j];
         sa.slot[j].pairs = pairs_dev + (size_t)j * (size_t)batch * 2;
         all_img = all_img && sa.slot[j].img;
     }
-    GradArgs &g = sa.ga.g;
-    g.ring = *ring;
-    g.head = head; g.filled = filled; g.batch = batch;
-    g.seed = seed; g.counter = counter;
-    g.explicit_idx = pairs_dev;
-    g.perm = replay_perm(seed, counter, 1u, (uint32_t)ring->n_agents);
-    g.local = nullptr; g.target = nullptr; g.partials = nullptr; g.img = nullptr;
-    g.n_actions = nets[0]->n_actions; g.dueling = nets[0]->dueling; g.kind = kind;
-    g.gamma = gamma; g.huber = huber;
-    g.P = uavenv_dqn_num_params(nets[0]);
-    g.dbg = nullptr;
-    g.is_w = nullptr;
-    g.abs_td = nullptr;
-    sa.ga.n_tiles = batch / kTile;
-    sa.ga.stride = uavenv_dqn_partial_stride(nets[0]);
-    const int grid = uavenv_dqn_partial_rows(batch);
-    // every slot with an image: both layer-1 images by LDS-DMA, as uavenv_dqn_grad_img stages them (UAVENV_STAGE_VGPR=1 keeps the
-    // register-staged form); otherwise the register-staged kernel, in which a slot without an image converts fc1 -- same values
-    static const bool stage_vgpr = getenv("UAVENV_STAGE_VGPR") && atoi(getenv("UAVENV_STAGE_VGPR")) != 0;
-    const int rc = all_img && !stage_vgpr ? launch_grad_slots<true>(sa, grid, n_nets, (hipStream_t)stream)
-                                          : launch_grad_slots<false>(sa, grid, n_nets, (hipStream_t)stream);
-    if (rc != UAVENV_OK) return rc;
-    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+    grad_args_fill(sa.ga, ring, head, filled, batch, seed, counter, pairs_dev, nets[0], kind, gamma, huber);
+    const dim3 grid(uavenv_dqn_partial_rows(batch), n_nets);
+    // every slot with an image: both layer-1 images by LDS-DMA, as uavenv_dqn_grad_img stages them; otherwise the register-staged
+    // kernel, in which a slot without an image converts fc1 -- same values
+    return all_img && !stage_vgpr() ? launch<k_dqn_grad_slots<true>>(grid, 512, kGradP8Lds, (hipStream_t)stream, sa)
+                                    : launch<k_dqn_grad_slots<false>>(grid, 512, kGradP8Lds, (hipStream_t)stream, sa);
 }
 
 int uavenv_dqn_grad_slots(const UavReplayRing *ring, int32_t head, int32_t filled, int32_t batch, uint64_t seed, uint64_t counter,
@@ -2544,12 +2186,8 @@ int uavenv_dqn_reduce_adam_slots_img(const UavDqnNet *const *nets, int32_t n_net
     for (int j = 0; j < n_nets; ++j) {
         const UavDqnNet *n = nets[j];
         float *im = images ? images[j] : nullptr;
-        if (!net_ok(n) || !n->target || !n->m || !n->v || !partials[j] || step_t[j] <= 0) return UAVENV_EINVAL;
-        if (im && (n->w != kW || n->hid != kHid || (((uintptr_t)im) & 15u) != 0)) return UAVENV_EINVAL;
-        if (n->n_actions != nets[0]->n_actions || (n->dueling != 0) != (nets[0]->dueling != 0)) return UAVENV_EINVAL;
-        if ((((uintptr_t)partials[j]) & 15u) != 0) return UAVENV_EINVAL;
-        for (int i = 0; i < j; ++i)
-            if (nets[i]->local == n->local || partials[i] == partials[j]) return UAVENV_EINVAL;
+        if (!slot_ok(nets, partials, j) || !n->target || !n->m || !n->v || step_t[j] <= 0) return UAVENV_EINVAL;
+        if (im && (n->w != kW || n->hid != kHid || !al16(im))) return UAVENV_EINVAL;
         const float bc2 = 1.0f - powf(beta2, (float)step_t[j]);
         a.slot[j].partials = partials[j];
         a.slot[j].local = n->local; a.slot[j].target = n->target; a.slot[j].m = n->m; a.slot[j].v = n->v;

@@ -766,18 +766,25 @@ __device__ __forceinline__ uint4 policy_philox(int i, uint64_t seed, uint64_t co
                          make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
 }
 
-__device__ __forceinline__ int policy_select(floatx4 q, uint4 rn, float eps, int n_actions)
+// (q: anything indexable holding NMAX Q values -- a floatx4, a float[NMAX])
+template <int NMAX, typename Q>
+__device__ __forceinline__ int policy_select_n(const Q &q, uint4 rn, float eps, int n_actions)
 {
     const float sample = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
     if (sample > eps) {
         int act = 0;
         float bq = q[0];
 #pragma unroll
-        for (int k = 1; k < 4; ++k)
+        for (int k = 1; k < NMAX; ++k)
             if (k < n_actions && q[k] > bq) { bq = q[k]; act = k; }
         return act;
     }
     return (int)(((uint64_t)rn.y * (uint64_t)n_actions) >> 32);
+}
+
+__device__ __forceinline__ int policy_select(floatx4 q, uint4 rn, float eps, int n_actions)
+{
+    return policy_select_n<4>(q, rn, eps, n_actions);
 }
 
 // PolicyNetContinuous_SAC.forward after fc_mu / fc_std (BaseCNN.py:470-483, quirks included: std = tanh(softplus(.)), the log-prob

@@ -1,0 +1,45 @@
+// The body of k_dqn_reduce_adam and k_dqn_reduce_adam_slots (learner.hip includes this text into both) behind their argument
+// unpacking.  In scope where it is included, under k_dqn_reduce_adam's parameter names: partials, nblk, P, stride, local, target,
+// m, v, lr, beta1, beta2, eps, bc1, bc2_sqrt, hard_update, loss, raw, go_word, go_value, img.
+//
+// Why text and not a function.  k_dqn_reduce_adam's instruction stream is held fixed (scripts/isa_account.py --compare), and
+// behind a __forceinline__ function with these parameters both kernels kept their 570 instructions and every register count but
+// issued the early loads of m / v / w in another order and moved one shift: five lines of the listing.
+    // gated update (uavenv_dqn_reduce_adam_gated): the step kernel of this pass stamps go_word with go_value when it moved at
+    // least one agent; a pass in which every agent had already finished leaves the learner exactly as it is (the reference's loop
+    // has left run_eposide by then, Envs/PathPlan_City.py:456-459)
+    UAV_HOT_PRIO();
+    if (go_word && __hip_atomic_load(go_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != go_value) return;
+    __shared__ float cnt_part[4];
+    const int tid = (int)threadIdx.x;
+    const int p = (int)blockIdx.x * 32 + tid;
+    // this parameter's moments and value are requested FIRST: their round trip runs under the partial rows' (behind the
+    // reduction's barriers they were a second, dependent round trip of the launch)
+    float m0 = 0.0f, v0 = 0.0f, w0 = 0.0f;
+    if (tid < 32 && p < P) { m0 = m[p]; v0 = v[p]; w0 = local[p]; }
+    float c;
+    const float t = reduce_columns(partials, nblk, P, stride, c);
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    if ((tid & 63) == 0) cnt_part[tid >> 6] = c;
+    __syncthreads();
+    const float cnt = (cnt_part[0] + cnt_part[1]) + (cnt_part[2] + cnt_part[3]);
+    const float inv = 1.0f / (cnt > 1.0f ? cnt : 1.0f);
+    if (tid < 32 && p < P + 2) {
+        if (raw) raw[p] = t;
+        if (p < P) {
+            const float gp = t * inv;
+            const float mp = m0 + (gp - m0) * (1.0f - beta1);
+            const float vp = v0 * beta2 + (1.0f - beta2) * gp * gp;
+            m[p] = mp;
+            v[p] = vp;
+            const float np = w0 - (lr / bc1) * (mp / (sqrtf(vp) / bc2_sqrt + eps));
+            local[p] = np;
+            if (hard_update) target[p] = np;
+            if (img) {                        // the C loop's layer-1 image follows the parameters (qnet_device.hpp: img_store_param)
+                img_store_param(img, p, np);
+                if (hard_update) img_store_param(img + kSplitF, p, np);
+            }
+        } else if (p == P && loss) {
+            *loss = t * inv;
+        }
+    }

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Instruction accounting of the gradient-kernel family's gfx950 machine code (CPU only, no GPU run).
 
-    python scripts/isa_account.py <tag>            -> profiles/isa_account_<tag>.txt
+    python scripts/isa_account.py <tag>                      -> profiles/isa_account_<tag>.txt
+    python scripts/isa_account.py <tag> --compare OTHER_CSRC -> profiles/isa_compare_<tag>.txt   (two trees, kernel by kernel)
 
 Compiles csrc/learner.hip device-only for gfx950 with _build.FLAGS (minus -shared / -ldl) plus -gline-tables-only, disassembles
-it with source lines (llvm-objdump -d -l) and writes, for k_dqn_grad_packed8<true>, k_dqn_grad_packed8<false>,
-k_dqn_grad_slots<true> and k_dqn_reduce_adam:
+it with source lines (llvm-objdump -d -l) and writes, for the gradient, reduce and acting kernels listed in KERNELS:
 
   * the instruction count per class (moves, nops, waits, LDS, global, MFMA, other VALU, scalar ALU, scalar memory, branches,
     lane reads and writes),
@@ -16,6 +16,10 @@ k_dqn_grad_slots<true> and k_dqn_reduce_adam:
 
 It lists what is in the listing, class by mnemonic prefix; it looks for no particular instruction.  -gline-tables-only changes
 no instruction: the tool checks that by comparing the per-kernel instruction counts with a build without it (--check-lines).
+
+--compare builds learner.hip, uavenv.hip, sac.hip and replay.hip of two trees without line tables and sets every kernel's listing
+and descriptor figures side by side: identical or not, instruction counts, registers, spills, scratch, waves per SIMD; the kernels of
+MUST_MATCH and of MUST_MATCH_FILES have to be identical (exit status 1 otherwise).  --diff-lines N prints the listing diff.
 """
 from __future__ import annotations
 
@@ -31,7 +35,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from dqn_based_uav_3d_path_planer_amd import _build  # noqa: E402
 
-KERNELS = ["k_dqn_grad_packed8<true>", "k_dqn_grad_packed8<false>", "k_dqn_grad_slots<true>", "k_dqn_reduce_adam"]
+KERNELS = ["k_dqn_grad_packed8<true>", "k_dqn_grad_packed8<false>", "k_dqn_grad_slots<true>", "k_dqn_grad_slots<false>",
+           "k_dqn_reduce_adam", "k_dqn_reduce_adam_slots",
+           "k_dqn_act<float, 4>", "k_dqn_act<float, 14>", "k_dqn_act<__half, 4>", "k_dqn_act<__half, 14>",
+           "k_dqn_act_packed<4>", "k_dqn_act_packed<14>", "k_dqn_act_slots<4>", "k_dqn_act_slots<14>",
+           "k_dqn_act_h<1, 4>", "k_dqn_act_h<2, 4>"]
+# --compare: the kernels whose instruction stream has to be the other tree's, instruction for instruction (the single-learner loops
+# and the benchmark are timed on them), next to every kernel of the files in MUST_MATCH_FILES
+MUST_MATCH = ["k_dqn_grad_packed8<true>", "k_dqn_grad_packed8<false>", "k_dqn_reduce_adam"]
+MUST_MATCH_FILES = ["uavenv", "sac", "replay"]
+COMPARE_FILES = ["learner"] + MUST_MATCH_FILES
 CLASSES = ["move", "nop", "wait", "barrier", "lds", "global", "mfma", "lane", "valu", "smem", "branch", "salu"]
 CLASS_TEXT = {"move": "register moves (v_mov_*)", "nop": "nops (s_nop)", "wait": "waits (s_waitcnt*)", "barrier": "workgroup barriers",
               "lds": "LDS (ds_*)", "global": "global / flat / buffer / scratch", "mfma": "MFMA (v_mfma_*)",
@@ -231,13 +244,86 @@ def account(name: str, ins, desc) -> list:
     return L
 
 
+def waves_per_simd(desc) -> int:
+    """occupancy step of a gfx950 kernel from its unified register count (the note's vgpr figure is VGPRs + AGPRs): 512 per lane
+    and SIMD, allocated in eights, 8 waves at most"""
+    regs = (desc.get("vgpr", 0) + 7) // 8 * 8
+    return min(8, 512 // max(regs, 8))
+
+
+def compare(other_csrc: str, this_csrc: str, diff_lines: int, files) -> tuple:
+    """(report lines, ok): every kernel of COMPARE_FILES in `other_csrc` against the same kernel in `this_csrc`, built without line
+    tables: (mnemonic, operands) sequences (addresses and branch-target annotations are no part of them; a branch's operand is its
+    relative distance) and the descriptor figures"""
+    import difflib
+    FIG = ["vgpr", "agpr", "sgpr", "vgpr_spills", "sgpr_spills", "scratch", "static_lds"]
+    L, ok = [], True
+    with tempfile.TemporaryDirectory() as td:
+        from concurrent.futures import ThreadPoolExecutor
+
+        def build(job):
+            side, csrc, f = job
+            obj = os.path.join(td, "%s_%s.o" % (f, side))
+            compile_device(os.path.join(csrc, f + ".hip"), obj, False)
+            return (side, f), (disassemble(obj, False), descriptors(obj))
+        with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+            built = dict(ex.map(build, [(side, csrc, f) for side, csrc in (("a", other_csrc), ("b", this_csrc)) for f in files]))
+    for f in files:
+        (da, ka), (db, kb) = built["a", f], built["b", f]
+        L.append("=" * 100)
+        L.append("%s.hip: %d kernels in the other tree, %d in this tree" % (f, len(ka), len(kb)))
+        L.append("  %-58s %7s %7s  %-9s %s" % ("kernel", "other", "this", "stream", "descriptor (vgpr agpr sgpr spills v/s scratch lds; waves/SIMD)"))
+        for k in sorted(set(ka) | set(kb)):
+            if k not in ka or k not in kb:
+                L.append("  %-58s only in %s tree" % (k, "the other" if k in ka else "this"))
+                ok = False
+                continue
+            sa, sb = [(m, o) for m, o, _ in da[k]], [(m, o) for m, o, _ in db[k]]
+            fa, fb = [ka[k].get(x, -1) for x in FIG], [kb[k].get(x, -1) for x in FIG]
+            same = sa == sb and fa == fb
+            must = f in MUST_MATCH_FILES or k in MUST_MATCH
+            fig = lambda v, d: "%d %d %d %d/%d %d %d; %d" % (v[0], v[1], v[2], v[3], v[4], v[5], v[6], waves_per_simd(d))
+            L.append("  %-58s %7d %7d  %-9s %s%s" % (k, len(sa), len(sb), "identical" if sa == sb else "DIFFERENT",
+                                                   fig(fa, ka[k]) if fa == fb else "%s -> %s" % (fig(fa, ka[k]), fig(fb, kb[k])),
+                                                   "   <-- MUST MATCH" if must and not same else ""))
+            if must and not same:
+                ok = False
+            if sa != sb and diff_lines:
+                ta, tb = ["%s %s" % x for x in sa], ["%s %s" % x for x in sb]
+                d = [x for x in difflib.unified_diff(ta, tb, "other", "this", n=1, lineterm="")][2:]
+                L.append("      %d lines removed, %d added" % (sum(x.startswith("-") for x in d), sum(x.startswith("+") for x in d)))
+                L += ["      " + x for x in d[:diff_lines]]
+                if len(d) > diff_lines:
+                    L.append("      ... (%d more diff lines)" % (len(d) - diff_lines))
+    L.append("")
+    L.append("gate (identical stream and descriptor for %s and every kernel of %s): %s" % (
+        ", ".join(MUST_MATCH), ", ".join(x + ".hip" for x in MUST_MATCH_FILES), "HOLDS" if ok else "BROKEN"))
+    return L, ok
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("tag")
+    ap.add_argument("--compare", metavar="CSRC", default=None,
+                    help="compare mode: the csrc directory of another tree (e.g. an export of the parent commit); writes "
+                         "profiles/isa_compare_<tag>.txt and exits 1 if a must-match kernel moved")
+    ap.add_argument("--files", nargs="+", choices=COMPARE_FILES, default=None, help="compare mode: only these files (default: all four)")
+    ap.add_argument("--diff-lines", type=int, default=0, help="compare mode: print up to this many diff lines per changed kernel")
     ap.add_argument("--csrc", default=_build.CSRC, help="directory holding learner.hip (default: this tree's csrc)")
     ap.add_argument("--out", default=None, help="output file (default profiles/isa_account_<tag>.txt)")
     ap.add_argument("--check-lines", action="store_true", help="also build without -gline-tables-only and compare the counts")
     args = ap.parse_args()
+    if args.compare:
+        L, ok = compare(args.compare, args.csrc, args.diff_lines, args.files or COMPARE_FILES)
+        flags = " ".join(f for f in _build.FLAGS if f not in ("-shared", "-ldl"))
+        head = ["Listing comparison, tag '%s' (scripts/isa_account.py --compare; CPU only): 'other' = the tree given, 'this' = this tree." % args.tag,
+                "  hipcc %s --cuda-device-only --no-gpu-bundle-output -c <file>.hip ; llvm-objdump -d --no-show-raw-insn -C ; llvm-readelf --notes" % flags,
+                "A stream is the sequence of (mnemonic, operands); instruction counts are given per kernel.", ""]
+        out = args.out or os.path.join(ROOT, "profiles", "isa_compare_%s.txt" % args.tag)
+        with open(out, "w") as f:
+            f.write("\n".join(head + L) + "\n")
+        print(out)
+        return 0 if ok else 1
     src = os.path.join(args.csrc, "learner.hip")
     out = args.out or os.path.join(ROOT, "profiles", "isa_account_%s.txt" % args.tag)
     with tempfile.TemporaryDirectory() as td:
