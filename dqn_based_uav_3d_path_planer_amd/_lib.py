@@ -46,6 +46,8 @@ SYMBOLS = (
     "uavenv_dqn_slots_loop_set_eps", "uavenv_dqn_slots_loop_run", "uavenv_dqn_slots_loop_get",
     "uavenv_dqn_grad_slots", "uavenv_dqn_reduce_adam_slots", "uavenv_dqn_slots_loop_set_multi_update",
     "uavenv_fed_choice",
+    "uavenv_per_fill_frame_slots", "uavenv_per_rebuild_slots", "uavenv_per_sample_slots", "uavenv_per_weights_slots",
+    "uavenv_per_set_f32_slots_gated", "uavenv_dqn_grad_slots_w", "uavenv_dqn_slots_loop_set_per", "uavenv_dqn_slots_loop_get_per",
 )
 SAC_CRITIC_IN, SAC_ACTOR_PARAMS, SAC_CRITIC_PARAMS, SAC_ACTOR_STRIDE, SAC_CRITIC_STRIDE = 102, 6724, 10882, 6728, 21768
 
@@ -207,6 +209,12 @@ class UavDqnSlotsLoopConfig(C.Structure):
 
 class UavDqnSlotsLoopCursor(C.Structure):
     _fields_ = [("head", C.c_int32), ("filled", C.c_int32), ("counter", C.c_uint64), ("epoch", C.c_int32 * DQN_MAX_SLOTS)]
+
+
+class UavDqnSlotsPer(C.Structure):
+    _fields_ = [("per", UavPer * DQN_MAX_SLOTS), ("slots_dev", C.c_void_p), ("prio_dev", C.c_void_p), ("w_dev", C.c_void_p),
+                ("abs_dev", C.c_void_p), ("alpha", C.c_double), ("beta", C.c_double), ("beta_inc", C.c_double),
+                ("eps", C.c_double), ("clip", C.c_double)]
 
 
 class UavEnvError(RuntimeError):
@@ -495,6 +503,28 @@ def load() -> C.CDLL:
     lib.uavenv_dqn_slots_loop_run.argtypes = [vp, i32, vp]
     lib.uavenv_dqn_slots_loop_get.restype = C.c_int
     lib.uavenv_dqn_slots_loop_get.argtypes = [vp, C.POINTER(UavDqnSlotsLoopCursor)]
+    # (one tree per UAV slot: the trees as an array of n pointers to UavPer, host memory)
+    pers_pp = C.POINTER(C.POINTER(UavPer))
+    lib.uavenv_per_fill_frame_slots.restype = C.c_int
+    lib.uavenv_per_fill_frame_slots.argtypes = [pers_pp, i32, i64, i64, f64, vp, i64, vp]
+    lib.uavenv_per_rebuild_slots.restype = C.c_int
+    lib.uavenv_per_rebuild_slots.argtypes = [pers_pp, i32, i64, i64, f64, vp, i64, vp]
+    lib.uavenv_per_sample_slots.restype = C.c_int
+    lib.uavenv_per_sample_slots.argtypes = [pers_pp, i32, i32, u64, u64, vp, vp, vp]
+    lib.uavenv_per_weights_slots.restype = C.c_int
+    lib.uavenv_per_weights_slots.argtypes = [pers_pp, i32, vp, vp, i32, i64, f64, i32, vp, vp, vp]
+    lib.uavenv_per_set_f32_slots_gated.restype = C.c_int
+    lib.uavenv_per_set_f32_slots_gated.argtypes = [pers_pp, i32, vp, vp, i32, f64, f64, f64, vp, C.c_uint32, vp]
+    lib.uavenv_dqn_grad_slots_w.restype = C.c_int
+    lib.uavenv_dqn_grad_slots_w.argtypes = [C.POINTER(UavReplayRing), i32, i32, i32, u64, u64, vp, nets_pp, i32, i32, f32, i32, vp, vp,
+                                            vp, vp]
+    lib.uavenv_dqn_grad_slots_w_img.restype = C.c_int
+    lib.uavenv_dqn_grad_slots_w_img.argtypes = [C.POINTER(UavReplayRing), i32, i32, i32, u64, u64, vp, nets_pp, i32, i32, f32, i32, vp,
+                                                vp, vp, vp, vp]
+    lib.uavenv_dqn_slots_loop_set_per.restype = C.c_int
+    lib.uavenv_dqn_slots_loop_set_per.argtypes = [vp, C.POINTER(UavDqnSlotsPer)]
+    lib.uavenv_dqn_slots_loop_get_per.restype = C.c_int
+    lib.uavenv_dqn_slots_loop_get_per.argtypes = [vp, C.POINTER(C.c_double)]
     if lib.uavenv_abi_version() != ABI_VERSION:
         raise UavEnvError(f"libuavenv ABI {lib.uavenv_abi_version()} != binding {ABI_VERSION}")
     _LIB = lib

@@ -20,6 +20,12 @@ int uavenv_dqn_grad_slots_img(const UavReplayRing *ring, int32_t head, int32_t f
                               const int32_t *pairs_dev, const UavDqnNet *const *nets, int32_t n_nets, int32_t kind, float gamma,
                               int32_t huber, float *const *partials, const float *const *images, void *stream);
 
+// uavenv_dqn_grad_slots_w with the images of the nets as they are now (images[j] as above).
+int uavenv_dqn_grad_slots_w_img(const UavReplayRing *ring, int32_t head, int32_t filled, int32_t batch, uint64_t seed, uint64_t counter,
+                                const int32_t *pairs_dev, const UavDqnNet *const *nets, int32_t n_nets, int32_t kind, float gamma,
+                                int32_t huber, const float *is_weights_dev, float *abs_td_out_dev, float *const *partials,
+                                const float *const *images, void *stream);
+
 // uavenv_dqn_reduce_adam_slots that keeps images[j] current with the new parameters (uavenv_dqn_reduce_adam_img per slot), and
 // writes slot j's column sums to raw_out[j] (host array, nullable as a whole and per net) as uavenv_dqn_reduce_adam's raw_out.
 int uavenv_dqn_reduce_adam_slots_img(const UavDqnNet *const *nets, int32_t n_nets, float *const *partials, int32_t n_partials,

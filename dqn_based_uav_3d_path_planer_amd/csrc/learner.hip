@@ -1030,6 +1030,36 @@ __global__ void __launch_bounds__(512) k_dqn_grad_slots(GradSlotsArgs sa)
 #include "grad_packed8_body.inc"
 }
 
+// k_dqn_grad_slots under prioritised replay: slot y also has its importance weights (row y of is_weights [n][batch]) and its |TD|
+// output (row y of abs_td [n][batch]) in the table -- both mandatory here, so the body's branches on them fold.  The body is the
+// same text again: workgroup (x, y) writes the row, and the |TD| entries, that workgroup x of k_dqn_grad_packed8 writes for slot y
+// with that slot's weights, bit for bit.
+struct GradSlotsWArgs {
+    Grad2Args ga;
+    struct { const float *local, *target, *img; float *partials; const int32_t *pairs; const float *is_w; float *abs_td; } slot[kActMaxSlots];
+};
+
+template <bool GLDS>
+__global__ void __launch_bounds__(512) k_dqn_grad_slots_w(GradSlotsWArgs sa)
+{
+    UAV_HOT_PRIO();
+    const int y = (int)blockIdx.y;
+    GradArgs g = sa.ga.g;
+    g.local = sa.slot[y].local;
+    g.target = sa.slot[y].target;
+    g.img = sa.slot[y].img;
+    g.partials = sa.slot[y].partials;
+    g.explicit_idx = sa.slot[y].pairs;
+    g.is_w = sa.slot[y].is_w;
+    g.abs_td = sa.slot[y].abs_td;
+    __builtin_assume(g.explicit_idx != nullptr);
+    __builtin_assume(g.is_w != nullptr);
+    __builtin_assume(g.abs_td != nullptr);
+    g.dbg = nullptr;
+    const Grad2Args &ga = sa.ga;
+#include "grad_packed8_body.inc"
+}
+
 // =====================================================================================================================
 // f16 MFMA learner (UavDqnNet.mfma_dtype = 1; BASELINE configs[2]: "fp16 Q-net MFMA").
 //
@@ -1906,6 +1936,32 @@ bool slot_ok(const UavDqnNet *const *nets, float *const *partials, int j)
     return true;
 }
 
+// The table of a per-slot gradient launch (GradSlotsArgs or GradSlotsWArgs): checks of uavenv_dqn_grad_slots, then the common fields
+template <class SA>
+bool grad_slots_fill(SA &sa, bool &all_img, const UavReplayRing *ring, int32_t head, int32_t filled, int32_t batch, uint64_t seed,
+                            uint64_t counter, const int32_t *pairs_dev, const UavDqnNet *const *nets, int32_t n_nets, int32_t kind,
+                            float gamma, int32_t huber, float *const *partials, const float *const *images)
+{
+    if (!nets || !partials || !pairs_dev || n_nets < 1 || n_nets > kActMaxSlots) return false;
+    if (!grad_ring_ok(ring, head, batch) || ring->obs_dtype != UAVENV_OBS_PACKED || (((uintptr_t)pairs_dev) & 7u) != 0) return false;
+    all_img = true;
+    for (int j = 0; j < kActMaxSlots; ++j) sa.slot[j] = {};
+    for (int j = 0; j < n_nets; ++j) {
+        const UavDqnNet *n = nets[j];
+        if (!slot_ok(nets, partials, j) || !n->target || n->mfma_dtype != UAVENV_MFMA_F32 || !al16(n->local, n->target)) return false;
+        if (n->n_actions + (n->dueling ? 1 : 0) > 4) return false;                               // the packed8 family only
+        const float *im = images ? images[j] : nullptr;
+        sa.slot[j].local = n->local;
+        sa.slot[j].target = n->target;
+        sa.slot[j].img = (im && al16(im)) ? im : nullptr;       // (as uavenv_dqn_grad_img: such a net converts for itself)
+        sa.slot[j].partials = partials[j];
+        sa.slot[j].pairs = pairs_dev + (size_t)j * (size_t)batch * 2;
+        all_img = all_img && sa.slot[j].img;
+    }
+    grad_args_fill(sa.ga, ring, head, filled, batch, seed, counter, pairs_dev, nets[0], kind, gamma, huber);
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2140,24 +2196,10 @@ int uavenv_dqn_grad_slots_img(const UavReplayRing *ring, int32_t head, int32_t f
                               const int32_t *pairs_dev, const UavDqnNet *const *nets, int32_t n_nets, int32_t kind, float gamma,
                               int32_t huber, float *const *partials, const float *const *images, void *stream)
 {
-    if (!nets || !partials || !pairs_dev || n_nets < 1 || n_nets > kActMaxSlots) return UAVENV_EINVAL;
-    if (!grad_ring_ok(ring, head, batch) || ring->obs_dtype != UAVENV_OBS_PACKED || (((uintptr_t)pairs_dev) & 7u) != 0) return UAVENV_EINVAL;
     GradSlotsArgs sa;
     bool all_img = true;
-    for (int j = 0; j < kActMaxSlots; ++j) sa.slot[j] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int j = 0; j < n_nets; ++j) {
-        const UavDqnNet *n = nets[j];
-        if (!slot_ok(nets, partials, j) || !n->target || n->mfma_dtype != UAVENV_MFMA_F32 || !al16(n->local, n->target)) return UAVENV_EINVAL;
-        if (n->n_actions + (n->dueling ? 1 : 0) > 4) return UAVENV_EINVAL;                       // the packed8 family only
-        const float *im = images ? images[j] : nullptr;
-        sa.slot[j].local = n->local;
-        sa.slot[j].target = n->target;
-        sa.slot[j].img = (im && al16(im)) ? im : nullptr;       // (as uavenv_dqn_grad_img: such a net converts for itself)
-        sa.slot[j].partials = partials[j];
-        sa.slot[j].pairs = pairs_dev + (size_t)j * (size_t)batch * 2;
-        all_img = all_img && sa.slot[j].img;
-    }
-    grad_args_fill(sa.ga, ring, head, filled, batch, seed, counter, pairs_dev, nets[0], kind, gamma, huber);
+    if (!grad_slots_fill(sa, all_img, ring, head, filled, batch, seed, counter, pairs_dev, nets, n_nets, kind, gamma, huber, partials, images))
+        return UAVENV_EINVAL;
     const dim3 grid(uavenv_dqn_partial_rows(batch), n_nets);
     // every slot with an image: both layer-1 images by LDS-DMA, as uavenv_dqn_grad_img stages them; otherwise the register-staged
     // kernel, in which a slot without an image converts fc1 -- same values
@@ -2171,6 +2213,34 @@ int uavenv_dqn_grad_slots(const UavReplayRing *ring, int32_t head, int32_t fille
 {
     return uavenv_dqn_grad_slots_img(ring, head, filled, batch, seed, counter, pairs_dev, nets, n_nets, kind, gamma, huber, partials,
                                      nullptr, stream);
+}
+
+// (internal, csrc/dqn_slots_internal.hpp) uavenv_dqn_grad_slots_w with the images of the nets as they are now
+int uavenv_dqn_grad_slots_w_img(const UavReplayRing *ring, int32_t head, int32_t filled, int32_t batch, uint64_t seed, uint64_t counter,
+                                const int32_t *pairs_dev, const UavDqnNet *const *nets, int32_t n_nets, int32_t kind, float gamma,
+                                int32_t huber, const float *is_weights_dev, float *abs_td_out_dev, float *const *partials,
+                                const float *const *images, void *stream)
+{
+    GradSlotsWArgs sa;
+    bool all_img = true;
+    if (!is_weights_dev || !abs_td_out_dev || (((uintptr_t)is_weights_dev | (uintptr_t)abs_td_out_dev) & 3u) != 0) return UAVENV_EINVAL;
+    if (!grad_slots_fill(sa, all_img, ring, head, filled, batch, seed, counter, pairs_dev, nets, n_nets, kind, gamma, huber, partials, images))
+        return UAVENV_EINVAL;
+    for (int j = 0; j < n_nets; ++j) {
+        sa.slot[j].is_w = is_weights_dev + (size_t)j * (size_t)batch;
+        sa.slot[j].abs_td = abs_td_out_dev + (size_t)j * (size_t)batch;
+    }
+    const dim3 grid(uavenv_dqn_partial_rows(batch), n_nets);
+    return all_img && !stage_vgpr() ? launch<k_dqn_grad_slots_w<true>>(grid, 512, kGradP8Lds, (hipStream_t)stream, sa)
+                                    : launch<k_dqn_grad_slots_w<false>>(grid, 512, kGradP8Lds, (hipStream_t)stream, sa);
+}
+
+int uavenv_dqn_grad_slots_w(const UavReplayRing *ring, int32_t head, int32_t filled, int32_t batch, uint64_t seed, uint64_t counter,
+                            const int32_t *pairs_dev, const UavDqnNet *const *nets, int32_t n_nets, int32_t kind, float gamma,
+                            int32_t huber, const float *is_weights_dev, float *abs_td_out_dev, float *const *partials, void *stream)
+{
+    return uavenv_dqn_grad_slots_w_img(ring, head, filled, batch, seed, counter, pairs_dev, nets, n_nets, kind, gamma, huber,
+                                       is_weights_dev, abs_td_out_dev, partials, nullptr, stream);
 }
 
 // (internal, csrc/dqn_slots_internal.hpp) raw_out: n_nets pointers (host array, nullable as a whole and per net) receiving slot j's

@@ -705,8 +705,13 @@ int uavenv_sac_loop_run(UavSacLoop *l, int32_t n_steps, void *stream)
 //         -- or, with uavenv_dqn_slots_loop_set_multi_update, uavenv_dqn_grad_slots + uavenv_dqn_reduce_adam_slots: all slots in two launches
 // Driven from Python this is, per pass and slot, a strided gather, uavenv_dqn_act and a scatter, then the step, then per slot a
 // draw, the gradient and Adam.  Every launch goes through the library's own entry points: K passes from here == K passes of
-// the caller issuing them, bit for bit.  A struct of its own beside UavLoop: that one already serves prioritised replay, the
-// sample lag, both exchanges and the bank refresh, none of which exist here.
+// the caller issuing them, bit for bit.  A struct of its own beside UavLoop: that one also serves the sample lag, both exchanges
+// and the bank refresh, none of which exist here.
+// With prioritised replay (uavenv_dqn_slots_loop_set_per: one tree per slot over its column of the ring) the draw gives way to
+//     uavenv_per_rebuild_slots (fill and retire fused in), uavenv_per_sample_slots, uavenv_per_weights_slots,
+//     uavenv_dqn_grad_slots_w, uavenv_dqn_reduce_adam_slots, uavenv_per_set_f32_slots_gated
+// -- every phase one launch (the rebuild and the weights two) for all slots: 10 launches per learning pass whatever U is, and 3
+// (act, step, uavenv_per_fill_frame_slots) for a pass that does not learn.
 // =====================================================================================================================
 #include "dqn_slots_internal.hpp"
 
@@ -721,6 +726,10 @@ struct UavDqnSlotsLoop {
     float *img = nullptr;
     // uavenv_dqn_slots_loop_set_multi_update: the learning phase as one gradient and one Adam launch for all slots
     int32_t multi_update = 0;
+    // uavenv_dqn_slots_loop_set_per: one tree per slot; the learning phase is then always the one-launch form
+    bool per_on = false;
+    UavDqnSlotsPer per;
+    double per_beta = 0.0;
 };
 
 extern "C" {
@@ -786,7 +795,40 @@ int uavenv_dqn_slots_loop_set_multi_update(UavDqnSlotsLoop *l, int32_t on)
     if (!l) return UAVENV_EINVAL;
     const UavDqnNet &n0 = l->c.slot[0].net;
     if (on && n0.n_actions + (n0.dueling ? 1 : 0) > 4) return UAVENV_EINVAL;      // uavenv_dqn_grad_slots: the packed8 family only
+    if (!on && l->per_on) return UAVENV_EINVAL;                                   // prioritised replay has the one-launch form only
     l->multi_update = on ? 1 : 0;
+    return UAVENV_OK;
+}
+
+int uavenv_dqn_slots_loop_set_per(UavDqnSlotsLoop *l, const UavDqnSlotsPer *cfg)
+{
+    if (!l) return UAVENV_EINVAL;
+    if (!cfg) {
+        l->per_on = false;
+        return UAVENV_OK;
+    }
+    const UavDqnSlotsLoopConfig &c = l->c;
+    const UavDqnNet &n0 = c.slot[0].net;
+    if (n0.n_actions + (n0.dueling ? 1 : 0) > 4 || !c.ring.valid || c.batch <= 0) return UAVENV_EINVAL;
+    if (!cfg->slots_dev || !cfg->prio_dev || !cfg->w_dev || !cfg->abs_dev) return UAVENV_EINVAL;
+    const UavPer *pers[UAVENV_DQN_MAX_SLOTS];
+    for (int j = 0; j < c.n_slots; ++j) {
+        pers[j] = &cfg->per[j];
+        if (cfg->per[j].capacity != (int64_t)c.ring.frames * (int64_t)(c.ring.n_agents / c.n_slots)) return UAVENV_EINVAL;
+    }
+    // (count 0: the trees' own checks -- uavenv_per_fill_frame_slots has the list -- and nothing enqueued)
+    if (uavenv_per_fill_frame_slots(pers, c.n_slots, 0, 0, 0.0, nullptr, 0, nullptr) != UAVENV_OK) return UAVENV_EINVAL;
+    l->per = *cfg;
+    l->per_beta = cfg->beta;
+    l->per_on = true;
+    l->multi_update = 1;
+    return UAVENV_OK;
+}
+
+int uavenv_dqn_slots_loop_get_per(const UavDqnSlotsLoop *l, double *beta_out)
+{
+    if (!l || !beta_out) return UAVENV_EINVAL;
+    *beta_out = l->per_beta;
     return UAVENV_OK;
 }
 
@@ -835,7 +877,44 @@ int uavenv_dqn_slots_loop_run(UavDqnSlotsLoop *l, int32_t n_steps, void *stream)
         if (rc != UAVENV_OK) return rc;
         l->head = nxt;
         if (l->filled < R.frames - 1) l->filled += 1;
-        if (B > 0 && (int64_t)l->filled * (int64_t)envs >= (int64_t)(c.learn_start > B ? c.learn_start : B)) {
+        const bool learn_now = B > 0 && (int64_t)l->filled * (int64_t)envs >= (int64_t)(c.learn_start > B ? c.learn_start : B);
+        if (l->per_on) {                  // ReplayTree.push(error 0) for every slot's rows of the frame just written (its column of
+            const UavDqnSlotsPer &P = l->per;                             // the valid plane); the new head's rows are retired
+            const UavPer *pers[UAVENV_DQN_MAX_SLOTS];
+            for (int j = 0; j < U; ++j) pers[j] = &P.per[j];
+            const double per_new = pow(0.0 + P.eps, P.alpha);
+            const uint8_t *valid_t = R.valid + (size_t)t * n;
+            if (!learn_now) {
+                rc = uavenv_per_fill_frame_slots(pers, U, (int64_t)t * envs, envs, per_new, valid_t, (int64_t)nxt * envs, s);
+                if (rc != UAVENV_OK) return rc;
+            } else {                      // ReplayTree.sample: beta first (:155), selection, importance weights + (frame, agent)
+                l->per_beta = l->per_beta + P.beta_inc < 1.0 ? l->per_beta + P.beta_inc : 1.0;
+                rc = uavenv_per_rebuild_slots(pers, U, (int64_t)t * envs, envs, per_new, valid_t, (int64_t)nxt * envs, s);
+                if (rc != UAVENV_OK) return rc;
+                rc = uavenv_per_sample_slots(pers, U, B, c.seed + 7, l->counter, P.slots_dev, P.prio_dev, s);
+                if (rc != UAVENV_OK) return rc;
+                rc = uavenv_per_weights_slots(pers, U, P.slots_dev, P.prio_dev, B, (int64_t)l->filled * envs, l->per_beta, envs, P.w_dev,
+                                              c.draws_dev, s);
+                if (rc != UAVENV_OK) return rc;
+                float *partials[UAVENV_DQN_MAX_SLOTS], *loss[UAVENV_DQN_MAX_SLOTS];
+                int32_t step_t[UAVENV_DQN_MAX_SLOTS], hard[UAVENV_DQN_MAX_SLOTS];
+                for (int j = 0; j < U; ++j) { partials[j] = c.slot[j].partials_dev; loss[j] = c.slot[j].loss_dev; }
+                rc = uavenv_dqn_grad_slots_w_img(&R, l->head, l->filled, B, c.seed, l->counter, c.draws_dev, nets, U, c.kind, c.gamma,
+                                                 c.huber, P.w_dev, P.abs_dev, partials, img, s);
+                if (rc != UAVENV_OK) return rc;           // (no epoch has moved)
+                for (int j = 0; j < U; ++j) {
+                    l->epoch[j] += 1;
+                    step_t[j] = l->epoch[j];
+                    hard[j] = l->epoch[j] % c.update_loop == 0 ? 1 : 0;
+                }
+                rc = uavenv_dqn_reduce_adam_slots_img(nets, U, partials, uavenv_dqn_partial_rows(B), c.lr, c.beta1, c.beta2, c.adam_eps,
+                                                      step_t, hard, loss, nullptr, c.moved_dev, (uint32_t)uavenv_tick(c.env), img, s);
+                if (rc != UAVENV_OK) return rc;
+                rc = uavenv_per_set_f32_slots_gated(pers, U, P.slots_dev, P.abs_dev, B, P.eps, P.alpha, P.clip, c.moved_dev,
+                                                    (uint32_t)uavenv_tick(c.env), s);         // ReplayTree.batch_update (:215-222)
+                if (rc != UAVENV_OK) return rc;
+            }
+        } else if (learn_now) {
             rc = uavenv_replay_draw_slots(R.frames, envs, l->head, l->filled, B, U, c.valid_draws ? R.valid : nullptr, UAVENV_DRAW_MAX_TRIES,
                                           c.seed + 7, l->counter, c.draws_dev, s);
             if (rc != UAVENV_OK) return rc;

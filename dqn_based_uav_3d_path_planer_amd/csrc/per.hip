@@ -42,7 +42,17 @@ struct PerFill {
     const uint8_t *valid;
 };
 
-__global__ void __launch_bounds__(256) k_per_chunk_sum(UavPer p, PerFill f)
+// Every kernel below is a body (a __device__ function of the tree it works on) with two launch forms: the one-tree kernel, and a
+// _slots twin on dim3(x, n_slots) that takes a table of trees in its arguments and works on slot[blockIdx.y] -- wavefront-uniform,
+// so the tree's pointers come in by scalar loads and no VGPR holds them.  One text per body: slice y of a _slots launch is the
+// one-tree launch on tree y, bit for bit.
+constexpr int kPerMaxSlots = UAVENV_DQN_MAX_SLOTS;
+struct PerSlots {
+    UavPer per[kPerMaxSlots];
+};
+
+// (valid_stride: the flag of slot first + i is f.valid[i * valid_stride])
+__device__ __forceinline__ void chunk_sum_body(const UavPer &p, const PerFill &f, int64_t valid_stride)
 {
     __shared__ double red[256];
     __shared__ double leaf[kChunk];
@@ -55,7 +65,7 @@ __global__ void __launch_bounds__(256) k_per_chunk_sum(UavPer p, PerFill f)
         if (q < p.capacity) {
             const int64_t sl = slot_of(p, q);
             if (sl >= f.first && sl < f.first + f.count) {
-                v = (!f.valid || f.valid[sl - f.first]) ? f.value : 0.0;
+                v = (!f.valid || f.valid[(sl - f.first) * valid_stride]) ? f.value : 0.0;
                 p.prio[sl] = v;
             } else if (sl >= f.retire_first && sl < f.retire_first + f.count) {
                 p.prio[sl] = 0.0;
@@ -83,7 +93,16 @@ __global__ void __launch_bounds__(256) k_per_chunk_sum(UavPer p, PerFill f)
     if (threadIdx.x == 0) p.chunk_sum[blockIdx.x] = red[0];
 }
 
-__global__ void __launch_bounds__(256) k_per_prefix(UavPer p, int n_chunks)
+__global__ void __launch_bounds__(256) k_per_chunk_sum(UavPer p, PerFill f) { chunk_sum_body(p, f, 1); }
+
+// slot y's column of the frame's valid plane: rows e * n_slots + y
+__global__ void __launch_bounds__(256) k_per_chunk_sum_slots(PerSlots t, PerFill f)
+{
+    if (f.valid) f.valid += blockIdx.y;
+    chunk_sum_body(t.per[blockIdx.y], f, (int64_t)gridDim.y);
+}
+
+__device__ __forceinline__ void prefix_body(const UavPer &p, int n_chunks)
 {
     __shared__ double part[256];
     const int per = (n_chunks + 255) / 256;
@@ -109,10 +128,13 @@ __global__ void __launch_bounds__(256) k_per_prefix(UavPer p, int n_chunks)
     if (b0 < n_chunks && b0 + per >= n_chunks) p.chunk_prefix[n_chunks] = run;     // the total
 }
 
+__global__ void __launch_bounds__(256) k_per_prefix(UavPer p, int n_chunks) { prefix_body(p, n_chunks); }
+
+__global__ void __launch_bounds__(256) k_per_prefix_slots(PerSlots t, int n_chunks) { prefix_body(t.per[blockIdx.y], n_chunks); }
+
 // One wavefront per sample.
-__global__ void __launch_bounds__(256) k_per_sample(UavPer p, int n_chunks, int batch, const double *__restrict__ draws,
-                                                    uint64_t seed, uint64_t counter, int64_t *__restrict__ out_slot,
-                                                    double *__restrict__ out_prio)
+__device__ __forceinline__ void sample_body(const UavPer &p, int n_chunks, int batch, const double *__restrict__ draws, uint64_t seed,
+                                            uint64_t counter, int64_t *__restrict__ out_slot, double *__restrict__ out_prio)
 {
     const int lane = (int)threadIdx.x & 63;
     const int i = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
@@ -233,6 +255,22 @@ __global__ void __launch_bounds__(256) k_per_sample(UavPer p, int n_chunks, int 
     }
 }
 
+__global__ void __launch_bounds__(256) k_per_sample(UavPer p, int n_chunks, int batch, const double *__restrict__ draws,
+                                                    uint64_t seed, uint64_t counter, int64_t *__restrict__ out_slot,
+                                                    double *__restrict__ out_prio)
+{
+    sample_body(p, n_chunks, batch, draws, seed, counter, out_slot, out_prio);
+}
+
+// slot y draws under (seed + y, counter) into row y of out_slot [n_slots][batch] and of out_prio [n_slots][prio_stride]
+__global__ void __launch_bounds__(256) k_per_sample_slots(PerSlots t, int n_chunks, int batch, uint64_t seed, uint64_t counter,
+                                                          int64_t *__restrict__ out_slot, double *__restrict__ out_prio, int prio_stride)
+{
+    const int y = (int)blockIdx.y;
+    sample_body(t.per[y], n_chunks, batch, nullptr, seed + (uint64_t)y, counter, out_slot + (size_t)y * batch,
+                out_prio ? out_prio + (size_t)y * prio_stride : nullptr);
+}
+
 __global__ void k_per_set(UavPer p, const int64_t *__restrict__ slots, const double *__restrict__ abs_err, int n,
                           double epsilon, double alpha, double clip)
 {
@@ -252,8 +290,9 @@ __global__ void k_per_set(UavPer p, const int64_t *__restrict__ slots, const dou
     p.prio[s] = pow(e, alpha);
 }
 
-__global__ void k_per_set_f32(UavPer p, const int64_t *__restrict__ slots, const float *__restrict__ abs_err, int n,
-                              double epsilon, double alpha, double clip, const uint32_t *__restrict__ go_word, uint32_t go_value)
+__device__ __forceinline__ void set_f32_body(const UavPer &p, const int64_t *__restrict__ slots, const float *__restrict__ abs_err, int n,
+                                             double epsilon, double alpha, double clip, const uint32_t *__restrict__ go_word,
+                                             uint32_t go_value)
 {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= n) return;
@@ -267,14 +306,27 @@ __global__ void k_per_set_f32(UavPer p, const int64_t *__restrict__ slots, const
     p.prio[s] = pow(e, alpha);
 }
 
+__global__ void k_per_set_f32(UavPer p, const int64_t *__restrict__ slots, const float *__restrict__ abs_err, int n,
+                              double epsilon, double alpha, double clip, const uint32_t *__restrict__ go_word, uint32_t go_value)
+{
+    set_f32_body(p, slots, abs_err, n, epsilon, alpha, clip, go_word, go_value);
+}
+
+// slot y's n entries are row y of slots / abs_err [n_slots][n]: the run rule never looks across a row's end
+__global__ void k_per_set_f32_slots(PerSlots t, const int64_t *__restrict__ slots, const float *__restrict__ abs_err, int n,
+                                    double epsilon, double alpha, double clip, const uint32_t *__restrict__ go_word, uint32_t go_value)
+{
+    const size_t o = (size_t)blockIdx.y * (size_t)n;
+    set_f32_body(t.per[blockIdx.y], slots + o, abs_err + o, n, epsilon, alpha, clip, go_word, go_value);
+}
+
 // ReplayTree.sample's importance weights (:175-178): w_i = (n p_i / int(total)) ** -beta, then / max_i w_i.  Two launches:
 // the powers (one f64 pow per thread) with one maximum per workgroup, then the division by the maximum of those maxima
 // (fixed-order LDS trees: deterministic).  `w64` holds the unnormalised weights in between (it may alias the priorities),
 // `wg_max` one double per workgroup of the first launch.  (prio and w64 carry no __restrict__: uavenv_per_weights passes the same
 // buffer for both; each thread reads its priority before it writes its weight.)
-__global__ void __launch_bounds__(256) k_per_weights_pow(UavPer p, int n_chunks, const double *prio, int batch,
-                                                         double n_entries, double beta, double *w64,
-                                                         double *__restrict__ wg_max)
+__device__ __forceinline__ void weights_pow_body(const UavPer &p, int n_chunks, const double *prio, int batch, double n_entries,
+                                                 double beta, double *w64, double *__restrict__ wg_max)
 {
     __shared__ double red[256];
     double total = floor(p.chunk_prefix[n_chunks]);
@@ -295,9 +347,26 @@ __global__ void __launch_bounds__(256) k_per_weights_pow(UavPer p, int n_chunks,
     if (threadIdx.x == 0) wg_max[blockIdx.x] = red[0];
 }
 
-__global__ void __launch_bounds__(256) k_per_weights_norm(const int64_t *__restrict__ slots, const double *__restrict__ w64,
-                                                          const double *__restrict__ wg_max, int n_wg, int batch, int n_agents,
-                                                          float *__restrict__ w_out, int32_t *__restrict__ fa_out)
+__global__ void __launch_bounds__(256) k_per_weights_pow(UavPer p, int n_chunks, const double *prio, int batch,
+                                                         double n_entries, double beta, double *w64,
+                                                         double *__restrict__ wg_max)
+{
+    weights_pow_body(p, n_chunks, prio, batch, n_entries, beta, w64, wg_max);
+}
+
+// row y of prio [n_slots][batch + n_wg]: slot y's priorities, then its workgroup maxima
+__global__ void __launch_bounds__(256) k_per_weights_pow_slots(PerSlots t, int n_chunks, double *prio, int batch, double n_entries,
+                                                               double beta)
+{
+    double *row = prio + (size_t)blockIdx.y * (size_t)(batch + (int)gridDim.x);
+    weights_pow_body(t.per[blockIdx.y], n_chunks, row, batch, n_entries, beta, row, row + batch);
+}
+
+// (frame, agent) of tree slot s: (s / n_agents, (s % n_agents) * agent_mul + agent_add) -- (1, 0) for a tree over whole frames,
+// (n_slots, j) for UAV slot j's tree over its column of the frames
+__device__ __forceinline__ void weights_norm_body(const int64_t *__restrict__ slots, const double *__restrict__ w64,
+                                                  const double *__restrict__ wg_max, int n_wg, int batch, int n_agents, int agent_mul,
+                                                  int agent_add, float *__restrict__ w_out, int32_t *__restrict__ fa_out)
 {
     __shared__ double red[256];
     double mx = 0.0;
@@ -317,8 +386,25 @@ __global__ void __launch_bounds__(256) k_per_weights_norm(const int64_t *__restr
         const int64_t s = slots[i];
         const int64_t f = s / n_agents;
         fa_out[2 * i] = (int32_t)f;
-        fa_out[2 * i + 1] = (int32_t)(s - f * n_agents);
+        fa_out[2 * i + 1] = (int32_t)(s - f * n_agents) * agent_mul + agent_add;
     }
+}
+
+__global__ void __launch_bounds__(256) k_per_weights_norm(const int64_t *__restrict__ slots, const double *__restrict__ w64,
+                                                          const double *__restrict__ wg_max, int n_wg, int batch, int n_agents,
+                                                          float *__restrict__ w_out, int32_t *__restrict__ fa_out)
+{
+    weights_norm_body(slots, w64, wg_max, n_wg, batch, n_agents, 1, 0, w_out, fa_out);
+}
+
+__global__ void __launch_bounds__(256) k_per_weights_norm_slots(const int64_t *__restrict__ slots, const double *__restrict__ prio,
+                                                                int batch, int n_envs, float *__restrict__ w_out,
+                                                                int32_t *__restrict__ fa_out)
+{
+    const int y = (int)blockIdx.y, n_wg = (int)gridDim.x;
+    const double *row = prio + (size_t)y * (size_t)(batch + n_wg);
+    weights_norm_body(slots + (size_t)y * batch, row, row + batch, n_wg, batch, n_envs, (int)gridDim.y, y, w_out + (size_t)y * batch,
+                      fa_out ? fa_out + (size_t)y * batch * 2 : nullptr);
 }
 
 __global__ void k_per_fill(UavPer p, int64_t first, int64_t count, double value, const uint8_t *__restrict__ valid)
@@ -329,17 +415,52 @@ __global__ void k_per_fill(UavPer p, int64_t first, int64_t count, double value,
 }
 
 // the two fills of a replay step in one launch: [first, first + count) as k_per_fill, [zero_first, zero_first + count) <- 0
-__global__ void k_per_fill2(UavPer p, int64_t first, int64_t count, double value, const uint8_t *__restrict__ valid, int64_t zero_first,
-                            int64_t valid_stride)
+__device__ __forceinline__ void fill2_body(const UavPer &p, int64_t first, int64_t count, double value, const uint8_t *__restrict__ valid,
+                                           int64_t zero_first, int64_t valid_stride)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) p.prio[first + i] = (!valid || valid[i * valid_stride]) ? value : 0.0;
     else if (i < 2 * count) p.prio[zero_first + (i - count)] = 0.0;
 }
 
+__global__ void k_per_fill2(UavPer p, int64_t first, int64_t count, double value, const uint8_t *__restrict__ valid, int64_t zero_first,
+                            int64_t valid_stride)
+{
+    fill2_body(p, first, count, value, valid, zero_first, valid_stride);
+}
+
+__global__ void k_per_fill2_slots(PerSlots t, int64_t first, int64_t count, double value, const uint8_t *__restrict__ valid,
+                                  int64_t zero_first)
+{
+    fill2_body(t.per[blockIdx.y], first, count, value, valid ? valid + blockIdx.y : nullptr, zero_first, (int64_t)gridDim.y);
+}
+
 bool per_ok(const UavPer *p)
 {
     return p && p->prio && p->chunk_sum && p->chunk_prefix && p->capacity > 0 && p->rot >= 0 && p->rot < p->capacity;
+}
+
+
+// the trees of a _slots call: 1 to UAVENV_DQN_MAX_SLOTS, each per_ok, one capacity, plain slot order, group sums on all or on none,
+// no two sharing their priorities
+bool per_slots_ok(const UavPer *const *pers, int n_slots, PerSlots &t)
+{
+    if (!pers || n_slots < 1 || n_slots > kPerMaxSlots) return false;
+    for (int j = 0; j < kPerMaxSlots; ++j) t.per[j] = UavPer{nullptr, nullptr, nullptr, 0, 0, nullptr};
+    for (int j = 0; j < n_slots; ++j) {
+        const UavPer *p = pers[j];
+        if (!per_ok(p) || p->rot != 0 || p->capacity != pers[0]->capacity || (p->group_sum != nullptr) != (pers[0]->group_sum != nullptr))
+            return false;
+        for (int i = 0; i < j; ++i)
+            if (pers[i]->prio == p->prio) return false;
+        t.per[j] = *p;
+    }
+    return true;
+}
+
+bool frame_ok(int64_t capacity, int64_t first, int64_t count, int64_t retire_first)
+{
+    return first >= 0 && retire_first >= 0 && count >= 0 && first + count <= capacity && retire_first + count <= capacity;
 }
 
 }  // namespace
@@ -454,6 +575,68 @@ int uavenv_per_fill(const UavPer *p, int64_t first, int64_t count, double priori
     if (count == 0) return UAVENV_OK;
     hipLaunchKernelGGL(k_per_fill, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *p, first,
                        count, priority, valid_dev);
+    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+}
+
+int uavenv_per_fill_frame_slots(const UavPer *const *pers, int32_t n_slots, int64_t first, int64_t count, double priority,
+                                const uint8_t *valid_dev, int64_t retire_first, void *stream)
+{
+    PerSlots t;
+    if (!per_slots_ok(pers, n_slots, t) || !frame_ok(t.per[0].capacity, first, count, retire_first)) return UAVENV_EINVAL;
+    if (count == 0) return UAVENV_OK;
+    hipLaunchKernelGGL(k_per_fill2_slots, dim3((unsigned)((2 * count + 255) / 256), n_slots), dim3(256), 0, (hipStream_t)stream, t, first,
+                       count, priority, valid_dev, retire_first);
+    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+}
+
+int uavenv_per_rebuild_slots(const UavPer *const *pers, int32_t n_slots, int64_t first, int64_t count, double priority,
+                             const uint8_t *valid_dev, int64_t retire_first, void *stream)
+{
+    PerSlots t;
+    if (!per_slots_ok(pers, n_slots, t) || !frame_ok(t.per[0].capacity, first, count, retire_first)) return UAVENV_EINVAL;
+    const int nc = uavenv_per_num_chunks(t.per[0].capacity);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_per_chunk_sum_slots, dim3(nc, n_slots), dim3(256), 0, s, t,
+                       PerFill{first, count, retire_first, priority, valid_dev});
+    hipLaunchKernelGGL(k_per_prefix_slots, dim3(1, n_slots), dim3(256), 0, s, t, nc);
+    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+}
+
+int uavenv_per_sample_slots(const UavPer *const *pers, int32_t n_slots, int32_t batch, uint64_t seed, uint64_t counter,
+                            int64_t *out_slot_dev, double *out_prio_dev, void *stream)
+{
+    PerSlots t;
+    if (!per_slots_ok(pers, n_slots, t) || batch <= 0 || !out_slot_dev) return UAVENV_EINVAL;
+    hipLaunchKernelGGL(k_per_sample_slots, dim3((batch + 3) / 4, n_slots), dim3(256), 0, (hipStream_t)stream, t,
+                       uavenv_per_num_chunks(t.per[0].capacity), batch, seed, counter, out_slot_dev, out_prio_dev, batch + (batch + 255) / 256);
+    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+}
+
+int uavenv_per_weights_slots(const UavPer *const *pers, int32_t n_slots, const int64_t *slots_dev, double *prio_dev, int32_t batch,
+                             int64_t n_entries, double beta, int32_t n_envs, float *is_weights_out_dev, int32_t *pairs_out_dev,
+                             void *stream)
+{
+    PerSlots t;
+    if (!per_slots_ok(pers, n_slots, t) || !slots_dev || !prio_dev || !is_weights_out_dev || batch <= 0 || n_entries <= 0)
+        return UAVENV_EINVAL;
+    if (pairs_out_dev && n_envs <= 0) return UAVENV_EINVAL;
+    const dim3 grid((batch + 255) / 256, n_slots);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_per_weights_pow_slots, grid, dim3(256), 0, s, t, uavenv_per_num_chunks(t.per[0].capacity), prio_dev, batch,
+                       (double)n_entries, beta);
+    hipLaunchKernelGGL(k_per_weights_norm_slots, grid, dim3(256), 0, s, slots_dev, prio_dev, batch, n_envs > 0 ? n_envs : 1,
+                       is_weights_out_dev, pairs_out_dev);
+    return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
+}
+
+int uavenv_per_set_f32_slots_gated(const UavPer *const *pers, int32_t n_slots, const int64_t *slots_dev, const float *abs_err_dev,
+                                   int32_t batch, double epsilon, double alpha, double clip, const uint32_t *go_word_dev,
+                                   uint32_t go_value, void *stream)
+{
+    PerSlots t;
+    if (!per_slots_ok(pers, n_slots, t) || !slots_dev || !abs_err_dev || batch <= 0) return UAVENV_EINVAL;
+    hipLaunchKernelGGL(k_per_set_f32_slots, dim3((batch + 255) / 256, n_slots), dim3(256), 0, (hipStream_t)stream, t, slots_dev,
+                       abs_err_dev, batch, epsilon, alpha, clip, go_word_dev, go_value);
     return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
 }
 

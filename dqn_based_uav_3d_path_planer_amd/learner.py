@@ -608,12 +608,16 @@ def act_slots(learners, obs: torch.Tensor, eps: float, seed: int, counter: int, 
     _lib.check(rc, "uavenv_dqn_act_slots")
 
 
-def update_slots(learners, ring, batch: int, pairs: torch.Tensor, images=None):
+def update_slots(learners, ring, batch: int, pairs: torch.Tensor, images=None, is_weights: torch.Tensor = None,
+                 abs_td_out: torch.Tensor = None):
     """One learn_off_policy() of every UAV slot's learner in TWO launches (uavenv_dqn_grad_slots, uavenv_dqn_reduce_adam_slots):
     learners[j] trains on ITS `batch` (frame, agent) pairs pairs[j] of the packed ring -- bit for bit what
     learners[j].learn_from_ring(ring, batch, 0, 0, explicit_idx=pairs[j]) gives: flat blocks, epoch, loss (each learner's own
     `loss` cell).  pairs: contiguous int32 [U, batch, 2] on the device (DeviceReplayRing.draw_slots' layout).  images: one
-    split_image() tensor per learner (or None) -- the form the slots loop launches; they follow the new parameters."""
+    split_image() tensor per learner (or None) -- the form the slots loop launches; they follow the new parameters.
+    is_weights / abs_td_out (contiguous f32 [U, batch] on the device, both or neither; prioritised replay): slot j's
+    importance-sampling weights in its loss and |TD| of its samples out (uavenv_dqn_grad_slots_w) -- what
+    learners[j].learn_from_ring(..., is_weights=is_weights[j], abs_td_out=abs_td_out[j]) gives, bit for bit."""
     import ctypes as C
     from . import _lib
     ls = check_slot_learners(learners)
@@ -630,8 +634,16 @@ def update_slots(learners, ring, batch: int, pairs: torch.Tensor, images=None):
         raise ValueError("update_slots learns from a discrete (DQN-family) packed ring")
     if images is not None and len(images) != U:
         raise ValueError("images: one per learner")
-    if not pairs.is_cuda:
-        raise ValueError("pairs must be on the device")
+    if (is_weights is None) != (abs_td_out is None):
+        raise ValueError("is_weights and abs_td_out come together (the weighted update reads one and writes the other)")
+    for name, t in (("is_weights", is_weights), ("abs_td_out", abs_td_out)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == (U, int(batch)) and
+                                  t.is_contiguous()):
+            raise ValueError(name + " must be a contiguous float32 [U, batch] tensor")
+    if is_weights is not None and L0.n_actions + (1 if L0.dueling else 0) > 4:
+        raise ValueError("the weighted update of all slots takes heads of at most 4 layer-2 outputs")
+    if not pairs.is_cuda or (is_weights is not None and not (is_weights.is_cuda and abs_td_out.is_cuda)):
+        raise ValueError("pairs (and is_weights / abs_td_out) must be on the device")
     lib = _lib.load()
     batch = int(batch)
     nblk = lib.uavenv_dqn_partial_rows(batch)
@@ -642,8 +654,13 @@ def update_slots(learners, ring, batch: int, pairs: torch.Tensor, images=None):
     parts = (C.c_void_p * U)(*[L._partials.data_ptr() for L in ls])
     imgs = None if images is None else (C.c_void_p * U)(*[None if t is None else t.data_ptr() for t in images])
     s = torch.cuda.current_stream(pairs.device).cuda_stream
-    rc = lib.uavenv_dqn_grad_slots_img(C.byref(ring._c), ring.head, ring.filled, batch, 0, 0, pairs.data_ptr(), nets, U,
-                                       0 if L0.kind == "dqn" else 1, L0.gamma, L0.huber, parts, imgs, s)
+    if is_weights is None:
+        rc = lib.uavenv_dqn_grad_slots_img(C.byref(ring._c), ring.head, ring.filled, batch, 0, 0, pairs.data_ptr(), nets, U,
+                                           0 if L0.kind == "dqn" else 1, L0.gamma, L0.huber, parts, imgs, s)
+    else:
+        rc = lib.uavenv_dqn_grad_slots_w_img(C.byref(ring._c), ring.head, ring.filled, batch, 0, 0, pairs.data_ptr(), nets, U,
+                                             0 if L0.kind == "dqn" else 1, L0.gamma, L0.huber, is_weights.data_ptr(),
+                                             abs_td_out.data_ptr(), parts, imgs, s)
     _lib.check(rc, "uavenv_dqn_grad_slots")
     for L in ls:
         L.epoch += 1

@@ -349,14 +349,19 @@ class DQNSlotsHotLoop:
     """The off-policy loop with one fused DQN-family learner per UAV slot (Envs/PathPlan_City.py:59-69, :364-385), enqueued by
     csrc/loop.hip: per pass ONE act launch for all slots (uavenv_dqn_act_slots), the env step (replay write included), ONE draw
     of (frame, agent) pairs for all slots and per slot the gradient and Adam launches (with multi_update: one of each for all
-    slots) -- what the general run_eposide issues from Python slot by slot, without the interpreter between the launches.  Uniform replay on one GPU.  The ring cursor and the
+    slots) -- what the general run_eposide issues from Python slot by slot, without the interpreter between the launches.  One GPU; uniform replay, or with `pers` prioritised replay with
+    one tree per slot and one launch per phase for all slots.  The ring cursor and the
     learners' update counts live in the C object while the loop exists; `run` writes them back.  The learners' parameters may
     be replaced between two runs (a federated merge): every run rebuilds the layer-1 images its launches stage."""
 
     def __init__(self, ring: DeviceReplayRing, learners, batch: int, seed: int, eps: float = 0.1, counter: int = 0,
                  learn_start: int = 0, auto_reset: bool = True, skip_done: bool = True, info: torch.Tensor = None,
-                 gate_updates: bool = False, valid_draws: bool = None, multi_update: bool = False):
-        """valid_draws (default: on when finished agents are skipped and not restarted): the draws go over the valid rows only
+                 gate_updates: bool = False, valid_draws: bool = None, multi_update: bool = False, pers=None):
+        """pers: one replay.DevicePER per UAV slot (capacity ring.frames * n_envs, tree_order=False, shared hyper-parameters; all
+        slots or none) -- prioritised replay inside the C loop, every phase (new frame's priorities, rebuild, ReplayTree.sample,
+        importance weights, the weighted gradient, Adam, batch_update) ONE launch for all slots: 10 launches per learning pass.
+        It implies the one-launch update whatever multi_update says.
+        valid_draws (default: on when finished agents are skipped and not restarted): the draws go over the valid rows only
         (the reference never stores a row for a finished agent, Envs/PathPlan_City.py:456-459); gate_updates: no update of any
         slot behind a step that moved nobody (HotLoop has the story); multi_update: all slots' updates of a pass in one gradient
         and one Adam launch (uavenv_dqn_grad_slots, uavenv_dqn_reduce_adam_slots) -- same results, 5 launches per pass."""
@@ -379,6 +384,23 @@ class DQNSlotsHotLoop:
             raise ValueError("valid_draws needs skip_done (with auto-reset every stored row is valid)")
         if info is not None and not (info.dtype == torch.uint8 and tuple(info.shape) == (ring.frames, env.N) and info.is_contiguous()):
             raise ValueError("info must be a contiguous uint8 [frames, N] plane")
+        self._pers = list(pers) if pers is not None and any(p is not None for p in pers) else None
+        if self._pers is not None:
+            if len(self._pers) != len(ls) or any(p is None for p in self._pers):
+                raise ValueError("prioritised replay in the DQN slots loop: one DevicePER per UAV slot, all slots or none")
+            if batch <= 0:
+                raise ValueError("prioritised replay needs a batch")
+            if L0.n_actions + (1 if L0.dueling else 0) > 4:
+                raise ValueError("prioritised replay in the DQN slots loop takes heads of at most 4 layer-2 outputs")
+            p0 = self._pers[0]
+            for p in self._pers:         # one Trainer.xml: the trees share their hyper-parameters (and one beta serves them all)
+                if (p.alpha, p.beta, p.beta_inc, p.epsilon, p.clip) != (p0.alpha, p0.beta, p0.beta_inc, p0.epsilon, p0.clip):
+                    raise ValueError("the slots' prioritised replays must share their hyper-parameters")
+            if len({id(p) for p in self._pers}) != len(self._pers):
+                raise ValueError("the slots' prioritised replays must be distinct objects (one tree per UAV index)")
+            for p in self._pers:
+                if p.capacity != ring.frames * (env.N // len(ls)) or p._c.rot != 0:
+                    raise ValueError("each slot's DevicePER must cover ring.frames * n_envs slots in slot order (tree_order=False)")
         self.lib = _lib.load()
         self.ring, self.learners = ring, ls
         U, d = len(ls), env.device
@@ -412,7 +434,23 @@ class DQNSlotsHotLoop:
         self._h = C.c_void_p()
         _lib.check(self.lib.uavenv_dqn_slots_loop_create(C.byref(cfg), C.byref(self._h)), "uavenv_dqn_slots_loop_create")
         self.multi_update = False
-        if multi_update:
+        if self._pers is not None:
+            b = int(batch)
+            self._per_bufs = (torch.zeros((U, b), dtype=torch.int64, device=d),
+                              torch.zeros((U, b + (b + 255) // 256), dtype=torch.float64, device=d),
+                              torch.zeros((U, b), dtype=torch.float32, device=d), torch.zeros((U, b), dtype=torch.float32, device=d))
+            pc = _lib.UavDqnSlotsPer()
+            for j, p in enumerate(self._pers):
+                pc.per[j] = p._c
+            pc.slots_dev, pc.prio_dev, pc.w_dev, pc.abs_dev = (t.data_ptr() for t in self._per_bufs)
+            p0 = self._pers[0]
+            pc.alpha, pc.beta, pc.beta_inc, pc.eps, pc.clip = p0.alpha, p0.beta, p0.beta_inc, p0.epsilon, p0.clip
+            rc = self.lib.uavenv_dqn_slots_loop_set_per(self._h, C.byref(pc))
+            if rc != 0:
+                self.close()
+                _lib.check(rc, "uavenv_dqn_slots_loop_set_per")
+            self.multi_update = True
+        elif multi_update:
             self.set_multi_update(True)
         self.counter = int(counter)
         self.batch = int(batch)
@@ -458,3 +496,11 @@ class DQNSlotsHotLoop:
         for j, L in enumerate(self.learners):
             L.epoch = int(cur.epoch[j])
         self._seen = (cur.head, cur.filled, tuple(L.epoch for L in self.learners))
+        if self._pers is not None:
+            beta = C.c_double()
+            _lib.check(self.lib.uavenv_dqn_slots_loop_get_per(self._h, C.byref(beta)), "uavenv_dqn_slots_loop_get_per")
+            n_envs = self.ring.env.N // len(self._pers)
+            for p in self._pers:
+                p.beta = float(beta.value)
+                p.n_entries = self.ring.filled * n_envs
+                p._dirty = True

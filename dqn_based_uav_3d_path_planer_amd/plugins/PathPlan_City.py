@@ -103,6 +103,8 @@ class PathPlan_City:
         # (csrc/loop.hip: UavDqnSlotsLoop).  Off by default: the general path below draws epsilon-greedy from torch's generator and
         # existing configurations reproduce under torch.manual_seed; this path draws from Philox.  Everything the loop needs is
         # checked HERE (the trainers then come up fused on the f32 MFMA); when a condition fails the general path runs.
+        # IsPriority_Replay = 1 stays on this path with one tree per UAV slot (csrc/per.hip: every phase one launch for all slots),
+        # for heads of at most 4 layer-2 outputs: the weighted gradient of all slots has no wider form.
         n2 = n_actions + (1 if tcfg.get("Trainer_Type") == "DuelingDQN_Trainer" else 0)
         self._want_fast_slots = (int(None2Value(param.get("fast_path"), 1)) != 0 and int(None2Value(param.get("fused_slots"), 0)) != 0 and
                                  1 < self.num_UAV <= 8 and
@@ -110,7 +112,7 @@ class PathPlan_City:
                                  param.get("obs_dtype") is None and
                                  int(None2Value(tcfg.get("Batch_Size"), 128)) % 64 == 0 and
                                  int(None2Value(tcfg.get("fused"), 1)) != 0 and (tcfg.get("mfma") or "f32") == "f32" and
-                                 int(None2Value(tcfg.get("IsPriority_Replay"), 0)) == 0 and
+                                 (int(None2Value(tcfg.get("IsPriority_Replay"), 0)) == 0 or n2 <= 4) and
                                  int(None2Value(tcfg.get("w"), 1)) == 100 and int(None2Value(tcfg.get("hiden_dim"), 64)) == 64 and
                                  n_actions >= 2 and n2 + 2 <= 16 and
                                  str(tcfg.get("device") or param.get("device") or "cuda").startswith("cuda") and
@@ -237,9 +239,11 @@ class PathPlan_City:
             for u in self.Agents:
                 u.Trainer.replay_memory = _RingMemoryView(ring, per_frame=self.num_envs)
         self.fast_slots = bool(self._want_fast_slots and getattr(self.backend, "packed", False) and
-                               all(getattr(u.Trainer, "fused", False) and getattr(u.Trainer.learner, "mfma", None) == "f32" and
-                                   getattr(u.Trainer, "IsPriority_Replay", 0) == 0 for u in self.Agents))
-        self._slots_hot, self._slots_counter = None, 0
+                               all(getattr(u.Trainer, "fused", False) and getattr(u.Trainer.learner, "mfma", None) == "f32"
+                                   for u in self.Agents) and
+                               len({getattr(u.Trainer, "IsPriority_Replay", 0) == 1 for u in self.Agents}) == 1)   # all trainers or none
+        self._slots_hot, self._slots_counter, self._slots_per = None, 0, None
+        self.slots_loop_with_per = False
         if self.fast_slots:
             # one packed ring for all UAV slots, as the SAC path keeps it: slot j's replay memory is rows e * num_UAV + j of every
             # frame -- num_envs transitions per frame, replay_size transitions per trainer (one ReplayMemory per UAV)
@@ -248,6 +252,12 @@ class PathPlan_City:
             self._info = torch.zeros((self._ring.frames, self.backend.N), dtype=torch.uint8, device=self.backend.device)
             for u in self.Agents:
                 u.Trainer.replay_memory = _RingMemoryView(self._ring, per_frame=self.num_envs)
+            if getattr(tr0, "IsPriority_Replay", 0) == 1:
+                # one priority per stored transition of each UAV slot (data slot = frame * num_envs + env), as the SAC path keeps
+                # them; sampled, weighted and updated inside the C loop, all slots per launch
+                from dqn_based_uav_3d_path_planer_amd.replay import DevicePER
+                self._slots_per = [DevicePER(self._ring.frames * self.num_envs, device=self.backend.device, tree_order=False)
+                                   for _ in self.Agents]
         # UAV.path of env 0 (UAV.py:431) and the path.csv the reference rewrites at every terminal (:461-464,:479-483,
         # :505-509).  One 16-double read-back of env 0's agents per step; <record_path>0</record_path> turns it off.
         self.record_path = int(None2Value(param.get("record_path"), 0 if (self.fast or self.fast_sac or self.fast_slots) else 1))
@@ -657,7 +667,8 @@ class PathPlan_City:
         frame, the env step (replay write included), one draw of every slot's Batch_Size transitions over ITS valid rows, and
         one gradient and one Adam launch for all slots (:364-385, :456; multi_update: measured faster than the per-slot launches
         at both shapes of profiles/dqn_slots_update_times.json, bit-identical results; heads of more than 4 layer-2 outputs keep
-        the per-slot launches, the only form that takes them).  The host reads back, every done_check passes, how many agents
+        the per-slot launches, the only form that takes them).  With IsPriority_Replay = 1 the draw is ReplayTree.sample on one
+        tree per slot and the update is weighted, every phase one launch for all slots.  The host reads back, every done_check passes, how many agents
         each step moved and the info counts, as _run_eposide_fused; updates behind a step that moved nobody are gated off on the
         device, and the counters follow."""
         from dqn_based_uav_3d_path_planer_amd.loop import DQNSlotsHotLoop
@@ -680,8 +691,12 @@ class PathPlan_City:
         if self._slots_hot is None:
             self._slots_hot = DQNSlotsHotLoop(ring, Ls, batch_now, seed=self.seed, eps=eps_rate, counter=self._slots_counter,
                                               learn_start=trs[0].Batch_Size + 1, auto_reset=False, skip_done=True, info=self._info,
-                                              gate_updates=True, multi_update=Ls[0].n_actions + int(Ls[0].dueling) <= 4)
+                                              gate_updates=True, multi_update=Ls[0].n_actions + int(Ls[0].dueling) <= 4,
+                                              pers=self._slots_per if train else None)
         hot = self._slots_hot
+        pers = self._slots_per if hot._pers is not None else None
+        self.slots_loop_with_per = pers is not None
+        beta0 = pers[0].beta if pers is not None else None
         hot.set_eps(eps_rate if train else 0.0)
         k = 1 if self.record_path else min(self.done_check, ring.frames - 2)
         n_steps, ended, passes = 0, False, 0
@@ -713,12 +728,18 @@ class PathPlan_City:
         surplus = passes - n_steps
         for L, e0 in zip(Ls, epoch0):        # the gated passes changed nothing on the device: one update per moving step
             L.epoch -= min(surplus, L.epoch - e0)
+        if pers is not None:                 # (beta moves with every update; every slot took the same number)
+            for p in pers:
+                p.beta = min(1.0, beta0 + (Ls[0].epoch - epoch0[0]) * p.beta_inc)
         self.surplus_passes_last_episode = surplus
         self._slots_counter = hot.counter - surplus
         if surplus > 0:                      # ... and neither the replay cursor nor the Philox counter remembers them
             hot.close()
             self._slots_hot = None
             self._rewind_ring(surplus)
+            if pers is not None:
+                for p in pers:
+                    p.n_entries = ring.filled * self.num_envs
         items = []
         for uav in self.Agents:
             tr = uav.Trainer

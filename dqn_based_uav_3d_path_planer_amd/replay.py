@@ -312,6 +312,70 @@ class DevicePER:
         return slots, w, p
 
 
+# ---- one DevicePER per UAV slot, one launch per phase for all of them (csrc/per.hip, the _slots entry points) -----------------------
+# Thin wrappers: `pers` is the list of the slots' DevicePER objects (tree j covers UAV slot j's column of the ring: tree slot
+# frame * n_envs + env <-> agent env * U + j), tensors are slot-major and on the trees' device, nothing is copied or synchronised.
+def _per_table(pers):
+    pers = list(pers)
+    if not pers or len(pers) > _lib.DQN_MAX_SLOTS:
+        raise ValueError("one DevicePER per UAV slot: 1 to %d of them" % _lib.DQN_MAX_SLOTS)
+    return pers, (C.POINTER(_lib.UavPer) * len(pers))(*[C.pointer(p._c) for p in pers])
+
+
+def per_fill_frame_slots(pers, first: int, count: int, priority: float, valid: torch.Tensor, retire_first: int):
+    """uavenv_per_fill_frame_slots: tree j's slots [first, first + count) <- priority where valid[i * U + j] (0 elsewhere; valid None:
+    everywhere), [retire_first, retire_first + count) <- 0."""
+    pers, tab = _per_table(pers)
+    _lib.check(pers[0].lib.uavenv_per_fill_frame_slots(tab, len(pers), int(first), int(count), float(priority),
+                                                       None if valid is None else valid.data_ptr(), int(retire_first),
+                                                       pers[0]._stream()), "uavenv_per_fill_frame_slots")
+    for p in pers:
+        p._dirty = True
+
+
+def per_rebuild_slots(pers, first: int = 0, count: int = 0, priority: float = 0.0, valid: torch.Tensor = None, retire_first: int = 0):
+    """uavenv_per_rebuild_slots: every tree's chunk sums (with that fill and retire applied on the way when count > 0) and prefix."""
+    pers, tab = _per_table(pers)
+    _lib.check(pers[0].lib.uavenv_per_rebuild_slots(tab, len(pers), int(first), int(count), float(priority),
+                                                    None if valid is None else valid.data_ptr(), int(retire_first),
+                                                    pers[0]._stream()), "uavenv_per_rebuild_slots")
+    for p in pers:
+        p._dirty = False
+
+
+def per_sample_slots(pers, batch: int, seed: int, counter: int, slots_out: torch.Tensor, prio_out: torch.Tensor):
+    """uavenv_per_sample_slots: slot j draws under Philox (seed + j, counter); slots_out int64 [U, batch], prio_out f64
+    [U, batch + (batch + 255) // 256].  Needs a current rebuild."""
+    pers, tab = _per_table(pers)
+    _lib.check(pers[0].lib.uavenv_per_sample_slots(tab, len(pers), int(batch), int(seed) & (2 ** 64 - 1), int(counter), slots_out.data_ptr(),
+                                                   None if prio_out is None else prio_out.data_ptr(), pers[0]._stream()),
+               "uavenv_per_sample_slots")
+
+
+def per_weights_slots(pers, slots: torch.Tensor, prio: torch.Tensor, batch: int, n_entries: int, beta: float, n_envs: int,
+                      w_out: torch.Tensor, pairs_out: torch.Tensor = None):
+    """uavenv_per_weights_slots: importance weights (f32 [U, batch]) normalised per slot, and the (frame, agent) pairs
+    (int32 [U, batch, 2]) of every draw.  `prio` is overwritten."""
+    pers, tab = _per_table(pers)
+    _lib.check(pers[0].lib.uavenv_per_weights_slots(tab, len(pers), slots.data_ptr(), prio.data_ptr(), int(batch), int(n_entries),
+                                                    float(beta), int(n_envs), w_out.data_ptr(),
+                                                    None if pairs_out is None else pairs_out.data_ptr(), pers[0]._stream()),
+               "uavenv_per_weights_slots")
+
+
+def per_set_f32_slots(pers, slots: torch.Tensor, abs_errors: torch.Tensor, batch: int, go=None):
+    """uavenv_per_set_f32_slots_gated: ReplayTree.batch_update of every slot from its row of slots / abs_errors ([U, batch]);
+    go = (device word, value) as DevicePER.update_f32.  The trees share epsilon, alpha and clip (those of pers[0] are used)."""
+    pers, tab = _per_table(pers)
+    gw, gv = go if go is not None else (None, 0)
+    p0 = pers[0]
+    _lib.check(p0.lib.uavenv_per_set_f32_slots_gated(tab, len(pers), slots.data_ptr(), abs_errors.data_ptr(), int(batch), p0.epsilon,
+                                                     p0.alpha, p0.clip, gw, int(gv) & 0xffffffff, p0._stream()),
+               "uavenv_per_set_f32_slots_gated")
+    for p in pers:
+        p._dirty = True
+
+
 def select_actions(env: VecPathPlanEnv, q: torch.Tensor, eps: float, seed: int, counter: int,
                    index_out: torch.Tensor = None, steer_out: torch.Tensor = None):
     """Fused epsilon-greedy over [N, A] Q-values (Trainer/DuelingDQN_Trainer.py:86-97)."""

@@ -356,6 +356,36 @@ int uavenv_per_set_f32_gated(const UavPer *per, const int64_t *slots_dev, const 
 int uavenv_per_weights(const UavPer *per, const int64_t *slots_dev, double *prio_dev, int32_t batch,
                        int64_t n_entries, double beta, int32_t n_agents, float *is_weights_out_dev,
                        int32_t *frame_agent_out_dev, void *stream);
+/* ---- the same for one tree per UAV slot in ONE launch per phase (grid x n_slots; tree j = pers[j], a HOST array of n_slots
+ * pointers).  Slice j of each launch is the per-tree kernel on tree j: every result is bit for bit what the per-tree entry point
+ * named below gives for pers[j].  UAVENV_EINVAL, with nothing enqueued (no device is touched), for: n_slots < 1 or
+ * > UAVENV_DQN_MAX_SLOTS; a NULL tree or one the per-tree entry refuses; capacities that differ; rot != 0; group_sum on some trees
+ * only; two trees sharing `prio`; batch <= 0; n_entries <= 0. */
+/* uavenv_per_fill_frame_strided(pers[j], first, count, priority, valid_dev + j, n_slots, retire_first) for every j: slot j reads the
+ * flag of tree slot first + i at valid_dev[i * n_slots + j] (its column of a frame's valid plane). */
+int uavenv_per_fill_frame_slots(const UavPer *const *pers, int32_t n_slots, int64_t first, int64_t count, double priority,
+                                const uint8_t *valid_dev, int64_t retire_first, void *stream);
+/* uavenv_per_rebuild_frame for every tree, the flags read as above: two launches, grids (num_chunks, n_slots) and (1, n_slots).
+ * count == 0: a plain uavenv_per_rebuild. */
+int uavenv_per_rebuild_slots(const UavPer *const *pers, int32_t n_slots, int64_t first, int64_t count, double priority,
+                             const uint8_t *valid_dev, int64_t retire_first, void *stream);
+/* uavenv_per_sample(pers[j], batch, NULL, seed + j, counter, out_slot_dev + j * batch, out_prio_dev + j * (batch + (batch + 255) / 256))
+ * for every j: out_slot_dev [n_slots][batch], out_prio_dev (nullable) [n_slots][batch + (batch + 255) / 256] -- the row uavenv_per_weights takes. */
+int uavenv_per_sample_slots(const UavPer *const *pers, int32_t n_slots, int32_t batch, uint64_t seed, uint64_t counter,
+                            int64_t *out_slot_dev, double *out_prio_dev, void *stream);
+/* uavenv_per_weights for every tree on row j of slots_dev / prio_dev (the layouts above): weights normalised by slot j's own maximum
+ * and the floor of slot j's own total, into is_weights_out_dev [n_slots][batch].  pairs_out_dev (nullable, [n_slots][batch][2]): tree j
+ * covers UAV slot j's column of the ring (tree slot s = frame * n_envs + env), and the pair written is
+ * (s / n_envs, (s % n_envs) * n_slots + j) -- (frame, AGENT), what uavenv_dqn_grad takes and uavenv_replay_draw_slots writes. */
+int uavenv_per_weights_slots(const UavPer *const *pers, int32_t n_slots, const int64_t *slots_dev, double *prio_dev, int32_t batch,
+                             int64_t n_entries, double beta, int32_t n_envs, float *is_weights_out_dev, int32_t *pairs_out_dev,
+                             void *stream);
+/* uavenv_per_set_f32_gated(pers[j], slots_dev + j * batch, abs_err_dev + j * batch, batch, ...) for every j, one gate word for all.
+ * The last of a run of equal slots writes, and a run lies within one slot's batch entries: the last entry of slot j and the first of
+ * slot j + 1 belong to different trees whatever numbers they hold. */
+int uavenv_per_set_f32_slots_gated(const UavPer *const *pers, int32_t n_slots, const int64_t *slots_dev, const float *abs_err_dev,
+                                   int32_t batch, double epsilon, double alpha, double clip, const uint32_t *go_word_dev,
+                                   uint32_t go_value, void *stream);
 
 /* ---- fused DQN-family learner for the reference's Q-MLPs (BaseClass/BaseCNN.py:93-139, w=100, hid=64) ---------- */
 /* Flat f32 parameter blocks in HBM (16-byte aligned), layout [W1 hid*w][b1 hid][W2 n2*hid][b2 n2] with n2 = n_actions
@@ -436,6 +466,13 @@ int uavenv_dqn_act_slots(const UavDqnNet *const *nets, int32_t n_nets, const voi
 int uavenv_dqn_grad_slots(const UavReplayRing *ring, int32_t head, int32_t filled, int32_t batch, uint64_t seed, uint64_t counter,
                           const int32_t *pairs_dev, const UavDqnNet *const *nets, int32_t n_nets, int32_t kind, float gamma,
                           int32_t huber, float *const *partials, void *stream);
+/* uavenv_dqn_grad_slots under prioritised replay: slot j also takes its importance weights is_weights_dev[j][batch] and writes
+ * |Q(s, a) - y| of its samples to abs_td_out_dev[j][batch] (both mandatory, f32, slot-major).  Row x of partials[j] and row j of
+ * abs_td_out_dev are bit for bit what uavenv_dqn_grad_w(ring, ..., pairs_dev + j * batch * 2, nets[j], kind, gamma, huber,
+ * is_weights_dev + j * batch, abs_td_out_dev + j * batch, partials[j]) writes.  Refuses what uavenv_dqn_grad_slots refuses. */
+int uavenv_dqn_grad_slots_w(const UavReplayRing *ring, int32_t head, int32_t filled, int32_t batch, uint64_t seed, uint64_t counter,
+                            const int32_t *pairs_dev, const UavDqnNet *const *nets, int32_t n_nets, int32_t kind, float gamma,
+                            int32_t huber, const float *is_weights_dev, float *abs_td_out_dev, float *const *partials, void *stream);
 /* uavenv_dqn_reduce_adam_gated for n_nets nets in ONE launch (grid (num_params + 2 + 31) / 32 x n_nets): slot j sums its
  * n_partials rows of partials[j] and takes Adam step step_t[j] (host array, each > 0: the slots' update counts may differ) with
  * the hard target copy where hard_update[j] != 0 (host array); loss_out (host array, nullable as a whole and per entry) holds
@@ -906,7 +943,8 @@ int uavenv_sac_loop_get_per(const UavSacLoop *loop, double *beta_out);
  * -- 3 + 2 n_slots launches, bit for bit what the same entry points give when the caller issues them.  The loop owns one layer-1
  * image per slot (the split form its act and gradient launches stage): rebuilt from the parameters whenever a run with
  * n_steps > 0 starts, kept current by its own Adam launches, so parameters may be replaced BETWEEN runs (a federated merge).
- * Uniform replay on one GPU only: no prioritised replay, no gradient exchange, no sample lag, no bank refresh. */
+ * One GPU only: no gradient exchange, no sample lag, no bank refresh.  Uniform replay unless uavenv_dqn_slots_loop_set_per gives every
+ * slot a tree (below): then a learning pass is 10 launches whatever n_slots is, and a pass that does not learn 3. */
 typedef struct UavDqnSlotsLoopSlot {
     UavDqnNet net;               /* f32 MFMA, w 100, hid 64; all slots one n_actions / dueling */
     float *partials_dev;         /* uavenv_dqn_partial_rows(batch) x uavenv_dqn_partial_stride(net) floats, this slot's own */
@@ -943,6 +981,31 @@ int uavenv_dqn_slots_loop_set_eps(UavDqnSlotsLoop *loop, float eps);
  * slots (a pass is 5 launches instead of 3 + 2 n_slots) -- same parameters, moments, losses and epochs, bit for bit.  Off by
  * default.  UAVENV_EINVAL, with the loop left as it was, when the loop's nets have more than 4 layer-2 outputs. */
 int uavenv_dqn_slots_loop_set_multi_update(UavDqnSlotsLoop *loop, int32_t on);
+/* Prioritised replay (IsPriority_Replay = 1), one tree per slot: per[j] covers slot j's column of the ring, tree slot
+ * frame * n_envs + env <-> agent env * n_slots + j, capacity frames * n_envs, rot 0.  One beta for all slots (one Trainer.xml, and every
+ * slot samples on every learning pass).  A pass then is, as in UavLoop and UavSacLoop:
+ *     act, step                          as above
+ *     not learning:                      uavenv_per_fill_frame_slots -- the frame just written gets (0 + eps) ** alpha where valid, the
+ *                                        new head frame is retired
+ *     learning (same condition):         beta = min(1, beta + beta_inc); uavenv_per_rebuild_slots with that fill fused in;
+ *                                        uavenv_per_sample_slots (seed + 7, c) -- slot j draws under seed + 7 + j;
+ *                                        uavenv_per_weights_slots with n_entries = filled * n_envs, the pairs into draws_dev;
+ *                                        uavenv_dqn_grad_slots_w; uavenv_dqn_reduce_adam_slots; uavenv_per_set_f32_slots_gated on moved_dev
+ * The learning phase is always the one-launch form (uavenv_dqn_slots_loop_set_multi_update(loop, 0) then returns UAVENV_EINVAL), and
+ * valid_draws has no meaning: invalid rows carry priority 0.  Call it before the first run; cfg NULL turns prioritised replay off
+ * (the one-launch update stays selected: same results; uavenv_dqn_slots_loop_set_multi_update changes it again).
+ * UAVENV_EINVAL, with the loop left as it was, for: more than 4 layer-2 outputs; no ring.valid; batch == 0; a NULL buffer; a capacity
+ * other than frames * n_envs; whatever uavenv_per_fill_frame_slots refuses of the trees. */
+typedef struct UavDqnSlotsPer {
+    UavPer per[UAVENV_DQN_MAX_SLOTS];
+    int64_t *slots_dev;          /* [n_slots][batch]: the tree slots of the last draw */
+    double *prio_dev;            /* [n_slots][batch + (batch + 255) / 256] */
+    float *w_dev;                /* [n_slots][batch]: importance weights */
+    float *abs_dev;              /* [n_slots][batch]: |TD| of the last gradient */
+    double alpha, beta, beta_inc, eps, clip;
+} UavDqnSlotsPer;
+int uavenv_dqn_slots_loop_set_per(UavDqnSlotsLoop *loop, const UavDqnSlotsPer *cfg);
+int uavenv_dqn_slots_loop_get_per(const UavDqnSlotsLoop *loop, double *beta_out);
 /* Enqueue n_steps passes on `stream`; never synchronises. */
 int uavenv_dqn_slots_loop_run(UavDqnSlotsLoop *loop, int32_t n_steps, void *stream);
 int uavenv_dqn_slots_loop_get(const UavDqnSlotsLoop *loop, UavDqnSlotsLoopCursor *out);

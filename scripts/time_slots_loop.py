@@ -19,6 +19,13 @@ uavenv_dqn_reduce_adam_slots), same shapes, same method, both forms first checke
 by a child process of its own under a time limit; the first failure ends the run.
     python scripts/time_slots_loop.py --multi-update [--out profiles/dqn_slots_update_times.json]
     python scripts/time_slots_loop.py --multi-update --profile-run     (the multi-update loop alone, for rocprofv3)
+--per times prioritised replay (one replay.DevicePER per slot): the C loop with DQNSlotsHotLoop(pers=...) -- every phase one launch for
+all slots, 10 launches per pass -- against the composition of the per-tree entry points issued from Python (per slot
+uavenv_per_rebuild_frame, uavenv_per_sample, uavenv_per_weights, the weighted update, uavenv_per_set_f32_gated), both checked equal
+on a short run first (ring planes, parameters, every tree's priorities, beta); the uniform multi-update loop of the same process is
+recorded next to them for information.  Same shapes, same method, one child process per shape.
+    python scripts/time_slots_loop.py --per [--out profiles/dqn_slots_per_times.json]
+    python scripts/time_slots_loop.py --per --profile-run     (the prioritised C loop alone, 500 passes at U = 4, for rocprofv3)
 """
 from __future__ import annotations
 
@@ -82,6 +89,105 @@ class Composition:
                 for j, L in enumerate(Ls):
                     L.learn_from_ring(ring, B, SEED, c, explicit_idx=self.draws[j * B:(j + 1) * B])
             self.counter += 1
+
+
+class PerComposition:
+    """The prioritised pass as the per-tree entry points give it, issued from Python slot by slot."""
+
+    def __init__(self, ring, Ls, pers, batch):
+        self.ring, self.Ls, self.pers, self.batch, self.counter = ring, Ls, pers, batch, 0
+        self.lib = _lib.load()
+        self.n_envs = ring.env.N // len(Ls)
+        self.a = torch.empty(self.n_envs, dtype=torch.int32, device=ring.env.device)
+        self.bufs = [p.make_bufs(batch) for p in pers]
+        self.beta = pers[0].beta
+
+    def run(self, passes):
+        import ctypes as C
+        import math
+        ring, Ls, pers, B, U, lib, n_envs = self.ring, self.Ls, self.pers, self.batch, len(self.Ls), self.lib, self.n_envs
+        s = torch.cuda.current_stream(ring.env.device).cuda_stream
+        p0 = pers[0]
+        per_new = math.pow(0.0 + p0.epsilon, p0.alpha)
+        for _ in range(passes):
+            c = self.counter
+            obs, act = ring.current_obs(), ring.current_action()
+            for j, L in enumerate(Ls):
+                L.act(obs[j::U].contiguous(), EPS, (SEED + j) & M64, c, index_out=self.a)
+                act[j::U] = self.a
+            t = ring.head
+            ring.step_env(auto_reset=True, skip_done=True)
+            nxt, valid_t = ring.head, ring.valid[t]
+            learn = ring.filled * n_envs >= B
+            if learn:
+                self.beta = self.beta + p0.beta_inc if self.beta + p0.beta_inc < 1.0 else 1.0
+            for j, (L, p, b) in enumerate(zip(Ls, pers, self.bufs)):
+                per = C.byref(p._c)
+                if not learn:
+                    _lib.check(lib.uavenv_per_fill_frame_strided(per, t * n_envs, n_envs, per_new, valid_t.data_ptr() + j, U,
+                                                                 nxt * n_envs, s), "uavenv_per_fill_frame_strided")
+                    continue
+                col = valid_t[j::U].contiguous()
+                _lib.check(lib.uavenv_per_rebuild_frame(per, t * n_envs, n_envs, per_new, col.data_ptr(), nxt * n_envs, s), "rebuild")
+                _lib.check(lib.uavenv_per_sample(per, B, None, (SEED + 7 + j) & M64, c, b["slots"].data_ptr(), b["prio"].data_ptr(), s),
+                           "sample")
+                _lib.check(lib.uavenv_per_weights(per, b["slots"].data_ptr(), b["prio"].data_ptr(), B, ring.filled * n_envs, self.beta,
+                                                  n_envs, b["w"].data_ptr(), b["pairs"].data_ptr(), s), "weights")
+                b["pairs"][:, 1] = b["pairs"][:, 1] * U + j
+                L.learn_from_ring(ring, B, SEED, c, explicit_idx=b["pairs"], is_weights=b["w"], abs_td_out=b["abs"])
+                _lib.check(lib.uavenv_per_set_f32_gated(per, b["slots"].data_ptr(), b["abs"].data_ptr(), B, p.epsilon, p.alpha, p.clip,
+                                                        None, 0, s), "set")
+            self.counter += 1
+
+
+def measure_per(n_envs, U, batch, ring_transitions, passes, windows, check_passes):
+    """The prioritised C loop against the prioritised composition from the same start; the uniform multi-update loop beside them."""
+    from dqn_based_uav_3d_path_planer_amd.replay import DevicePER
+    env_a, ring_a, La = build(n_envs, U, ring_transitions)
+    env_b, ring_b, Lb = build(n_envs, U, ring_transitions)
+    env_c, ring_c, Lc = build(n_envs, U, ring_transitions)
+    pers_a = [DevicePER(ring_a.frames * n_envs, device="cuda:0", tree_order=False) for _ in range(U)]
+    pers_b = [DevicePER(ring_b.frames * n_envs, device="cuda:0", tree_order=False) for _ in range(U)]
+    comp = PerComposition(ring_a, La, pers_a, batch)
+    loop = DQNSlotsHotLoop(ring_b, Lb, batch, seed=SEED, eps=EPS, auto_reset=True, skip_done=True, pers=pers_b)
+    uniform = DQNSlotsHotLoop(ring_c, Lc, batch, seed=SEED, eps=EPS, auto_reset=True, skip_done=True, multi_update=True)
+    comp.run(check_passes)
+    loop.run(check_passes)
+    torch.cuda.synchronize()
+    equal = all(torch.equal(getattr(ring_a, k), getattr(ring_b, k)) for k in ("obs", "action", "reward", "done", "valid"))
+    equal = equal and all(torch.equal(a.flat, b.flat) and a.epoch == b.epoch and float(a.loss) == float(b.loss) for a, b in zip(La, Lb))
+    equal = equal and (ring_a.head, ring_a.filled) == (ring_b.head, ring_b.filled) and La[0].epoch > 0
+    equal = equal and all(torch.equal(a.prio, b.prio) and torch.equal(a._chunk_prefix, b._chunk_prefix) for a, b in zip(pers_a, pers_b))
+    equal = equal and comp.beta == pers_b[0].beta and bool((pers_b[0].prio > 0).any())
+    if not equal:
+        raise SystemExit(f"U={U}: the prioritised C loop and the composition differ after {check_passes} passes")
+    warm = max(50, passes // 10)
+    for f in (comp, loop, uniform):
+        f.run(warm)
+    t_loop, t_comp, t_uni = [], [], []
+    for _ in range(windows):                          # the forms alternate
+        t_loop.append(window(loop.run, passes))
+        t_comp.append(window(comp.run, passes))
+        t_uni.append(window(uniform.run, passes))
+    N = env_a.N
+    res = {"uav_per_env": U, "n_envs": n_envs, "agents": N, "batch_per_slot": batch, "ring_frames": ring_a.frames,
+           "ring_transitions": (ring_a.frames - 1) * N, "passes_per_window": passes, "windows": windows,
+           "equal_after_passes": check_passes, "launches_per_pass_loop": 10, "launches_per_pass_per_slot_calls": 3 + 9 * U,
+           "launches_per_pass_uniform_multi_update": 5}
+    for name, t in (("loop", t_loop), ("composition", t_comp), ("uniform_multi_update_for_information", t_uni)):
+        med = float(np.median(t))
+        res[name] = {"us_per_pass_windows": [round(x, 3) for x in t], "us_per_pass_median": round(med, 3),
+                     "us_per_pass_min": round(min(t), 3), "us_per_pass_max": round(max(t), 3),
+                     "agent_steps_per_s": round(N / med * 1e6), "updates_per_s": round(U / med * 1e6)}
+    res["speedup_median"] = round(res["composition"]["us_per_pass_median"] / res["loop"]["us_per_pass_median"], 3)
+    # the condition for switching the plugin over: the loop's slowest window beats the composition's fastest
+    res["loop_faster_beyond_spread"] = bool(max(t_loop) < min(t_comp))
+    res["device"] = torch.cuda.get_device_name(0)
+    loop.close()
+    uniform.close()
+    for e in (env_a, env_b, env_c):
+        e.close()
+    return res
 
 
 def window(fn, passes):
@@ -180,8 +286,9 @@ ROWS = ((16384, 4), (32768, 2))                       # (envs, UAV slots): N = 6
 def multi_update_rows(a):
     """One child process per shape, each under its own time limit; the first failure ends the run."""
     shapes = []
+    mode = "--per" if a.per else "--multi-update"
     for n_envs, U in ROWS:
-        cmd = ["timeout", "-k", "10", str(a.row_timeout), sys.executable, os.path.abspath(__file__), "--multi-update", "--row",
+        cmd = ["timeout", "-k", "10", str(a.row_timeout), sys.executable, os.path.abspath(__file__), mode, "--row",
                str(n_envs), str(U), "--passes", str(a.passes), "--windows", str(a.windows), "--check-passes", str(a.check_passes)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
@@ -189,14 +296,19 @@ def multi_update_rows(a):
             raise SystemExit(f"the shape {n_envs} x {U} ended with status {r.returncode}: nothing further is started")
         shapes.append(json.loads(r.stdout.strip().splitlines()[-1]))
         print(json.dumps(shapes[-1]), flush=True)
+    key = "loop_faster_beyond_spread" if a.per else "multi_update_faster_beyond_spread"
     return {"device": shapes[0]["device"], "method": "device events around windows of passes, both forms warmed up, alternating in one "
             "process per shape, median of the windows; spread = min .. max of the windows", "shapes": shapes,
-            "multi_update_faster_beyond_spread_at_every_shape": all(x["multi_update_faster_beyond_spread"] for x in shapes)}
+            key + "_at_every_shape": all(x[key] for x in shapes)}
 
 
-def profile_run(passes, multi_update=False):
+def profile_run(passes, multi_update=False, per=False):
     env, ring, Ls = build(16384, 4, 1 << 20)
-    loop = DQNSlotsHotLoop(ring, Ls, 16384, seed=SEED, eps=EPS, auto_reset=True, skip_done=True, multi_update=multi_update)
+    pers = None
+    if per:
+        from dqn_based_uav_3d_path_planer_amd.replay import DevicePER
+        pers = [DevicePER(ring.frames * 16384, device="cuda:0", tree_order=False) for _ in range(4)]
+    loop = DQNSlotsHotLoop(ring, Ls, 16384, seed=SEED, eps=EPS, auto_reset=True, skip_done=True, multi_update=multi_update, pers=pers)
     loop.run(passes)
     torch.cuda.synchronize()
     loop.close()
@@ -211,12 +323,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--profile-run", action="store_true")
     ap.add_argument("--multi-update", action="store_true")
-    ap.add_argument("--row", type=int, nargs=2, metavar=("ENVS", "SLOTS"), help="(--multi-update's children) measure this shape only")
-    ap.add_argument("--row-timeout", type=int, default=420, help="seconds a --multi-update shape may take")
+    ap.add_argument("--per", action="store_true")
+    ap.add_argument("--row", type=int, nargs=2, metavar=("ENVS", "SLOTS"), help="(--multi-update's / --per's children) measure this shape only")
+    ap.add_argument("--row-timeout", type=int, default=420, help="seconds a --multi-update / --per shape may take")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join("profiles", "dqn_slots_update_times.json" if a.multi_update else "dqn_slots_loop_times.json")
-    if a.multi_update and not a.profile_run and a.row is None:     # (the parent never opens the device)
+        a.out = os.path.join("profiles", "dqn_slots_per_times.json" if a.per else
+                             "dqn_slots_update_times.json" if a.multi_update else "dqn_slots_loop_times.json")
+    if (a.multi_update or a.per) and not a.profile_run and a.row is None:     # (the parent never opens the device)
         out = multi_update_rows(a)
         os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
         with open(a.out, "w") as f:
@@ -225,10 +339,11 @@ def main():
         return
     assert torch.cuda.is_available(), "needs an MI355X"
     if a.profile_run:
-        profile_run(min(a.passes, 500), multi_update=a.multi_update)
+        profile_run(min(a.passes, 500), multi_update=a.multi_update, per=a.per)
         return
     if a.row is not None:
-        print(json.dumps(measure_update(a.row[0], a.row[1], 16384, 1 << 20, a.passes, a.windows, a.check_passes)))
+        fn = measure_per if a.per else measure_update
+        print(json.dumps(fn(a.row[0], a.row[1], 16384, 1 << 20, a.passes, a.windows, a.check_passes)))
         return
     out = {"device": torch.cuda.get_device_name(0), "method": "device events around windows of passes, both forms warmed up, "
            "alternating in one process, median of the windows; spread = min .. max of the windows",
