@@ -48,6 +48,7 @@ SYMBOLS = (
     "uavenv_fed_choice",
     "uavenv_per_fill_frame_slots", "uavenv_per_rebuild_slots", "uavenv_per_sample_slots", "uavenv_per_weights_slots",
     "uavenv_per_set_f32_slots_gated", "uavenv_dqn_grad_slots_w", "uavenv_dqn_slots_loop_set_per", "uavenv_dqn_slots_loop_get_per",
+    "uavenv_eval_episodes_f16",
 )
 SAC_CRITIC_IN, SAC_ACTOR_PARAMS, SAC_CRITIC_PARAMS, SAC_ACTOR_STRIDE, SAC_CRITIC_STRIDE = 102, 6724, 10882, 6728, 21768
 
@@ -464,6 +465,8 @@ def load() -> C.CDLL:
     lib.uavenv_fed_choice.argtypes = [vp, i32, i32, vp, i32, C.POINTER(C.POINTER(UavDqnNet)), i32, vp, vp, vp, vp]
     lib.uavenv_eval_episodes.restype = C.c_int
     lib.uavenv_eval_episodes.argtypes = [vp, C.POINTER(UavDqnNet), C.POINTER(UavEvalArgs), vp]
+    lib.uavenv_eval_episodes_f16.restype = C.c_int
+    lib.uavenv_eval_episodes_f16.argtypes = [vp, C.POINTER(UavDqnNet), C.POINTER(UavEvalArgs), vp]
     lib.uavenv_eval_episodes_slots.restype = C.c_int
     lib.uavenv_eval_episodes_slots.argtypes = [vp, C.POINTER(C.POINTER(UavDqnNet)), i32, C.POINTER(UavEvalArgs), vp]
     lib.uavenv_eval_episodes_sac.restype = C.c_int

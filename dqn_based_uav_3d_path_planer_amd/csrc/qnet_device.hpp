@@ -759,6 +759,82 @@ __device__ __forceinline__ void polh_wave(int p, const float *flat, int n_action
     __syncthreads();                             // Q values handed over
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same forward one 16-row strip at a time, for the whole-episode evaluation of f16-MFMA nets (k_eval_episodes_h,
+// uavenv.hip): the lanes build their rows from registers, so neither polh_wave's row copy nor its two-wavefront split fits.
+// Same operands in the same K positions of the same four v_mfma_f32_16x16x32_f16 per accumulator as polh_wave and
+// fwd_strip_h (learner.hip): the Q values are k_dqn_act_h's, bit for bit.
+// ---------------------------------------------------------------------------------------------------------------------
+// fc1 + b1 -> the f16 tile [64][kPolLdW] (column 100 = b1, 101..103 = 0), rounded as wh_commit and polh_wave round them; 256 threads
+__device__ __forceinline__ void polh_stage_tile(_Float16 *Wt, const NetDev &nl)
+{
+    const int tid = (int)threadIdx.x;
+    floatx4 v[kStageIters];
+    w_issue(v, nl.W1);
+    const float pb1 = nl.b1[tid < kHid ? tid : kHid - 1];
+#pragma unroll
+    for (int it = 0; it < kStageIters; ++it) {
+        const int c = it * 256 + tid;
+        if (c < kStageChunks) {
+            const int row = c / 25, q = c - row * 25;
+            *reinterpret_cast<half4 *>(Wt + row * kPolLdW + 4 * q) =
+                half4{(_Float16)v[it][0], (_Float16)v[it][1], (_Float16)v[it][2], (_Float16)v[it][3]};
+        }
+    }
+    if (tid < kHid)
+        *reinterpret_cast<half4 *>(Wt + tid * kPolLdW + kW) = half4{(_Float16)pb1, (_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f};
+}
+
+// A packed row in registers as one row of an f16 strip: kPolLdW halves at dst (LDS, 16-byte aligned) -- columns 0..99, column
+// 100 = 1.0, 101..103 = 0.  The halves are those an f16 env stores (store_obs_row / ctile_emit: static_cast<_Float16> of the f32
+// scalar) and those xh_commit<OBS_KIND_PACKED> expands a packed row to (the same cast of the same f32): flags are 0 / 1.0 exactly,
+// the 15 scalars round to nearest even.  Dword d holds columns 2 d and 2 d + 1; a pair never straddles a mask word, and the mask
+// bits of the scalar and constant-zero columns are 0.
+__device__ __forceinline__ void prow_store_half(_Float16 *dst, const PRow &R)
+{
+    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+    const uint32_t m[3] = {R.m0, R.m1, R.m2};
+    uint32_t d[52];
+#pragma unroll
+    for (int k = 6; k < 48; ++k) {                               // flag pairs (the dwords of scalars are overwritten below)
+        const uint32_t t = m[(2 * k) >> 5] >> ((2 * k) & 31);
+        d[k] = ((t & 1u) | ((t & 2u) << 15)) * 0x3c00u;          // 1.0 = 0x3c00
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) d[k] = __builtin_bit_cast(uint32_t, half2v{(_Float16)R.sc[2 * k], (_Float16)R.sc[2 * k + 1]});
+    d[5] = (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)R.sc[10]) | (((R.m0 >> 11) & 1u) * 0x3c000000u);   // column 10 | flag 11
+    d[43] = __builtin_bit_cast(uint32_t, half2v{(_Float16)R.sg[0], (_Float16)R.sg[1]});                        // columns 86..89
+    d[44] = __builtin_bit_cast(uint32_t, half2v{(_Float16)R.sg[2], (_Float16)R.sg[3]});
+    d[48] = d[49] = d[51] = 0u;                                   // columns 96..99, 102, 103
+    d[50] = 0x3c00u;                                              // column 100 = 1.0, 101 = 0
+#pragma unroll
+    for (int k = 0; k < 13; ++k) reinterpret_cast<uintx4 *>(dst)[k] = uintx4{d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]};
+}
+
+// acc[t][.] = pre-activations of hidden units 16 t + .. for the 16 rows of `strip` ([16][kPolLdW] halves, prow_store_half) against
+// the tile of polh_stage_tile: lane group g takes columns 32 kk + 8 g .. + 7 in K-steps 0..2; in K-step 3 group 0 takes
+// 96..99 | 100 (1.0 against b1) | three zeros and the other groups zeros.
+__device__ __forceinline__ void fwd_strip_polh(const _Float16 *Wt, const _Float16 *strip, floatx4 (&acc)[4])
+{
+    const int lane = (int)threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+    const _Float16 z = (_Float16)0.0f;
+    const _Float16 *xr = strip + r * kPolLdW;
+    half8 b[4];
+#pragma unroll
+    for (int kk = 0; kk < 3; ++kk) b[kk] = *reinterpret_cast<const half8 *>(xr + 32 * kk + 8 * g);
+    b[3] = g == 0 ? *reinterpret_cast<const half8 *>(xr + 96) : half8{z, z, z, z, z, z, z, z};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const _Float16 *wr = Wt + (16 * t + r) * kPolLdW;
+        half8 A[4];
+#pragma unroll
+        for (int kk = 0; kk < 3; ++kk) A[kk] = *reinterpret_cast<const half8 *>(wr + 32 * kk + 8 * g);
+        A[3] = g == 0 ? *reinterpret_cast<const half8 *>(wr + 96) : half8{z, z, z, z, z, z, z, z};
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) acc[t] = mfma16h(A[kk], b[kk], kk == 0 ? floatx4{0.0f, 0.0f, 0.0f, 0.0f} : acc[t]);
+    }
+}
+
 // epsilon-greedy over the Q values (Trainer/DuelingDQN_Trainer.py:86-97; the Philox stream of k_dqn_act*: rn of agent i)
 __device__ __forceinline__ uint4 policy_philox(int i, uint64_t seed, uint64_t counter)
 {

@@ -1832,6 +1832,129 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes(StepArgs a, EvalArgs v
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Greedy evaluation of an f16-MFMA net (uavenv_eval_episodes_f16; BASELINE configs[2]): k_eval_episodes' loop, line for line, with
+// the f16-MFMA forward of k_dqn_act_h as the policy -- what an f16 learner acts with, not its f32 master weights under the f32
+// forward.  fc1 + b1 are staged once per workgroup as the f16 tile of polh_wave ([64][kPolLdW], through registers: v.img is not
+// used, v.img_off is the tile's offset); fc2 / b2 stay f32.  The lane's row goes into a wave-private 16-row strip as 104 halves
+// (uavq::prow_store_half: the halves an f16 env stores and the halves k_dqn_act_h expands a packed row to are the same for every
+// state, so one instantiation serves both obs kinds), one strip at a time: the lanes of group st write, all 64 lanes run
+// uavq::fwd_strip_polh + w2_load / q_strip, lane 16 st + r keeps the result.  The strip takes the bytes of the observation queue.
+// ------------------------------------------------------------------------------------------------
+template <typename MaskT>
+__global__ void __launch_bounds__(256, 1) k_eval_episodes_h(StepArgs a, EvalArgs v)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int lane = (int)threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int tid = (int)threadIdx.x;
+    // ---- staging, once per workgroup: the world by LDS-DMA, fc1 + b1 (to f16) and fc2 / b2 through registers
+    _Float16 *Wt = reinterpret_cast<_Float16 *>(smem + v.img_off);  // [64][kPolLdW]
+    float *W2 = reinterpret_cast<float *>(smem + v.w2_off);        // [16][64]
+    float *b2 = W2 + uavq::kMaxOut * uavq::kHid;                    // [16]
+    if (wv >= 2) stage_copy_glds(smem, a, wv - 2, 2);               // (as k_eval_episodes: the world through wavefronts 2-3)
+    {
+        const uavq::NetDev nl = uavq::net_view(v.local, v.n2);
+        uavq::polh_stage_tile(Wt, nl);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (tid + 256 * k < v.n2 * uavq::kHid) W2[tid + 256 * k] = nl.W2[tid + 256 * k];
+        if (tid < v.n2) b2[tid] = nl.b2[tid];
+    }
+    Agent g = {};
+    EvalLane L = {};
+    L.e = (int)blockIdx.x * 256 + tid;                               // this lane's first episode (installed at the loop's top)
+    bool install = true;
+    __syncthreads();                                                 // world, fc1 tile, fc2 staged
+    const WorldLds<MaskT> w = world_view<MaskT>(smem, a);
+    unsigned char *slot = smem + v.slot_off + wv * v.slot_bytes;
+    ObsWaveLds *Q = reinterpret_cast<ObsWaveLds *>(slot);           // the observation work queue, then (same bytes) the strip
+    _Float16 *strip = reinterpret_cast<_Float16 *>(slot);           // [16][kPolLdW]
+    const int r16 = lane & 15, grp = lane >> 4;
+    const int A = a.n_actions;
+    for (;;) {
+        if (install) eval_install(a, v, g, L);                       // (one call site: the installation is inlined once)
+        install = false;
+        if (__ballot(L.e < v.n) == 0ull) break;
+        const bool have = L.e < v.n;
+        // ---- 1. state_PathPlan of the current state, as a packed row (store_obs_row_packed's layout) in registers
+        const ObsBits bits = obs_bits_queued(w, Q, g.o.px, g.o.py, g.o.pz, have);
+        const ObsScalars sc = obs_scalars(g.o, g.head);
+        uavq::PRow R;
+        ctile_mask_words(bits, R.m0, R.m1, R.m2);
+#pragma unroll
+        for (int k = 0; k < 11; ++k) R.sc[k] = sc.f[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) R.sg[k] = sc.f[11 + k];
+        if (!have) {                                                 // idle lane: a zero row, result discarded
+            R.m0 = R.m1 = R.m2 = 0u;
+#pragma unroll
+            for (int k = 0; k < 11; ++k) R.sc[k] = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) R.sg[k] = 0.0f;
+        }
+        wave_lds_sync();                                             // (the queue's last reads are done: the strip takes its bytes)
+        // ---- 2. Q(s) of the 64 rows: four 16-row strips, lane 16 st + r writes row r of strip st and keeps its result
+        float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+        for (int st = 0; st < 4; ++st) {
+            if (grp == st) uavq::prow_store_half(strip + r16 * uavq::kPolLdW, R);
+            wave_lds_sync();
+            uavq::floatx4 h[4];
+            uavq::fwd_strip_polh(Wt, strip, h);
+            uavq::W2Frag<4> F;
+            uavq::w2_load<4>(F, W2, b2, v.n2);
+            float qs[4];
+            uavq::q_strip<4>(h, F, v.n2, A, v.dueling, qs);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q[k] = grp == st ? qs[k] : q[k];
+            wave_lds_sync();                                         // the strip is read: the next strip (or the next queue) may take the bytes
+        }
+        if (have) {
+            // ---- the action: k_dqn_act_h's greedy branch (first maximum, strict >); eps > 0: a uniform action on a draw < eps
+            int act = 0;
+            float bq = q[0];
+#pragma unroll
+            for (int k = 1; k < 4; ++k)
+                if (k < A && q[k] > bq) { bq = q[k]; act = k; }
+            if (v.eps > 0.0f) {
+                const uint4 rn = philox4x32_10(make_uint4((uint32_t)L.e, (uint32_t)L.steps, 0u, 0xe75fu),
+                                               make_uint2((uint32_t)v.seed, (uint32_t)(v.seed >> 32)));
+                const float u = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
+                if (u < v.eps) act = (int)(((uint64_t)rn.y * (uint64_t)A) >> 32);
+            }
+            // ---- 3. update_PathPlan (UAV.py:397-513): step_agent's pieces
+            const int j = L.e % a.U;
+            const double a0 = decode_action(RawAction{(uint32_t)act, 0u}, UAVENV_ACT_INDEX_I32, A);
+            PreStep P;
+            step_pre(a, a0, g, P);
+            if (P.moved) g.head = angle_of<true>(g.o.vx, g.o.vy);   // :423
+            double r = 0.0;
+            int ret_done = 0, info = UAVENV_INFO_NORMAL;
+            bool head_set = false;
+            step_post<MaskT, false, true>(a, w, L.e, a0, g, P, r, ret_done, info, head_set);
+            g.o.n_rem = g.n_total - g.sub_idx;
+            L.steps += 1;
+            L.ret += r;
+            L.energy += fly_power(a.pw, g.o.V, j);
+            // a move always changes x or y (|V_vector| = Max_V > 0): the position is back where it was only after :425-428
+            if (P.moved && g.o.px == P.ox && g.o.py == P.oy && g.o.pz == P.oz) L.collisions += 1;
+            if (L.steps <= v.traj_steps) {
+                double *p = v.traj_pos + ((size_t)L.e * (v.traj_steps + 1) + L.steps) * 3;
+                p[0] = g.o.px; p[1] = g.o.py; p[2] = g.o.pz;
+                v.traj_act[(size_t)L.e * v.traj_steps + L.steps - 1] = (int8_t)act;
+            }
+            // ---- 4. the end of the episode: record, then the next episode of this lane
+            const bool trunc = (v.max_steps > 0 && L.steps >= v.max_steps) || L.steps >= L.cap;
+            if (g.done || trunc) {
+                const int outcome = g.done ? (info == UAVENV_INFO_LOSE ? UAVENV_EVAL_LOSE : UAVENV_EVAL_SUCCESS) : UAVENV_EVAL_TRUNCATED;
+                eval_store_record(v, L.e, g, L, outcome, j);
+                L.e += v.lanes;
+                install = true;
+            }
+        }
+    }
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // SAC policy evaluation (uavenv_eval_episodes_sac): k_eval_episodes with the continuous actor as the policy, APF or not.
@@ -3147,6 +3270,98 @@ int uavenv_eval_episodes(UavEnv *e, const UavDqnNet *net, const UavEvalArgs *arg
         return fail(UAVENV_EINVAL, "uavenv_eval_episodes: n %d + %d lanes exceeds the episode index range", u.n, v.lanes);
     if (e->mask_bytes == 4) hipLaunchKernelGGL(k_eval_episodes<uint32_t>, dim3(grid), dim3(256), lds, s, a, v);
     else hipLaunchKernelGGL(k_eval_episodes<uint64_t>, dim3(grid), dim3(256), lds, s, a, v);
+    HIP_TRY(hipGetLastError());
+    return UAVENV_OK;
+}
+
+// uavenv_eval_episodes for an f16-MFMA net on an f16 or packed env (k_eval_episodes_h).  Every refusal comes before anything is
+// allocated or enqueued; the kernel stages fc1 itself, so this entry needs no layer-1 image and allocates nothing at all.
+int uavenv_eval_episodes_f16(UavEnv *e, const UavDqnNet *net, const UavEvalArgs *args, void *stream)
+{
+    if (!e || !net || !args) return fail(UAVENV_EINVAL, "null argument");
+    const UavEvalArgs &u = *args;
+    if (e->cfg.apf_enabled == 1) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: APF envs are not supported");
+    if (e->cfg.obs_dtype != UAVENV_OBS_F16 && e->cfg.obs_dtype != UAVENV_OBS_PACKED)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: needs an env with f16 or packed observation rows");
+    if (!e->have_world) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16 before uavenv_set_buildings");
+    const int n2 = net->n_actions + (net->dueling ? 1 : 0);
+    if (!net->local || net->mfma_dtype != UAVENV_MFMA_F16 || net->w != uavq::kW || net->hid != uavq::kHid || net->n_actions < 2 ||
+        n2 > 4 || net->n_actions != e->cfg.n_actions)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: needs an f16-MFMA net of w %d, hid %d, the env's %d actions, <= 4 outputs",
+                    uavq::kW, uavq::kHid, e->cfg.n_actions);
+    if (u.n <= 0 || u.first < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: n %d, first %d", u.n, u.first);
+    if (!u.records || ((((uintptr_t)u.records) | ((uintptr_t)net->local)) & 15u) != 0)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: records and net->local must be 16-byte aligned device pointers");
+    const int given = (u.start_goal ? 1 : 0) + (u.sub ? 1 : 0) + (u.nsub ? 1 : 0);
+    if (given != 0 && given != 3) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: give all three scenario arrays or none");
+    if (given == 3 && u.m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: m %d", u.m);
+    if (given == 0 && e->bank_m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: no scenarios (the env has no bank)");
+    if (u.traj_steps < 0 || u.traj_steps >= (1 << 30) || (u.traj_steps > 0 && (!u.traj_pos || !u.traj_act)))
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: traj_steps %d needs both trajectory pointers", u.traj_steps);
+    if (u.max_steps < 0 || u.max_workgroups < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: max_steps / max_workgroups < 0");
+    if ((((uintptr_t)u.start_goal) | ((uintptr_t)u.sub) | ((uintptr_t)u.v0) | ((uintptr_t)u.traj_pos)) & 7u)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: misaligned f64 array");
+    if (((uintptr_t)u.nsub) & 3u) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: misaligned nsub");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+
+    // the env's parameters and world; the scenario set in the bank's place; nothing the step launches own
+    StepArgs a = base_args(e);
+    a.moved_word = nullptr;
+    a.meta = nullptr;
+    a.meta_a1 = nullptr;
+    a.dbg = nullptr;
+    a.block = 256;
+    if (given == 3) {
+        a.bank.start_goal = u.start_goal;
+        a.bank.sub = u.sub;
+        a.bank.nsub = u.nsub;
+        a.bank.m = u.m;
+    }
+    EvalArgs v;
+    memset(&v, 0, sizeof(v));
+    v.local = net->local;
+    v.v0 = u.v0;
+    v.rec = reinterpret_cast<uint4 *>(u.records);
+    v.traj_pos = u.traj_steps > 0 ? u.traj_pos : nullptr;
+    v.traj_act = u.traj_steps > 0 ? u.traj_act : nullptr;
+    v.seed = u.seed;
+    v.eps = u.eps;
+    v.n = u.n;
+    v.first = u.first;
+    v.max_steps = u.max_steps;
+    v.traj_steps = u.traj_steps;
+    v.n2 = n2;
+    v.dueling = net->dueling;
+    v.img_off = (e->world_bytes + 15) & ~15;       // the f16 fc1 tile (+ b1)
+    v.w2_off = v.img_off + uavq::kPolWBytes;
+    v.slot_off = (v.w2_off + (uavq::kMaxOut * uavq::kHid + uavq::kMaxOut) * 4 + 15) & ~15;
+    int slot = (int)sizeof(ObsWaveLds);            // the work queue, then (same bytes) the wavefront's 16-row strip of halves
+    if (slot < 16 * uavq::kPolLdW * 2) slot = 16 * uavq::kPolLdW * 2;
+    v.slot_bytes = (slot + 15) & ~15;
+    const size_t lds = (size_t)v.slot_off + 4 * (size_t)v.slot_bytes;
+    const void *fn = e->mask_bytes == 4 ? reinterpret_cast<const void *>(k_eval_episodes_h<uint32_t>)
+                                        : reinterpret_cast<const void *>(k_eval_episodes_h<uint64_t>);
+    if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // grid: as many workgroups as stay resident, at most one per 256 episodes (or max_workgroups)
+    const int want = (int)(((int64_t)u.n + 255) / 256);
+    int grid = want;
+    if (u.max_workgroups > 0) {
+        grid = u.max_workgroups < want ? u.max_workgroups : want;
+    } else {
+        int per_cu = 0, cus = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
+        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device));
+        const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+        if (resident < grid) grid = (int)resident;
+    }
+    if (grid < 1) grid = 1;
+    v.lanes = grid * 256;
+    // (a lane's next episode is e + lanes in 32-bit arithmetic: the last one taken must still be representable)
+    if ((int64_t)u.n + (int64_t)v.lanes > (int64_t)INT32_MAX)
+        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: n %d + %d lanes exceeds the episode index range", u.n, v.lanes);
+    if (e->mask_bytes == 4) hipLaunchKernelGGL(k_eval_episodes_h<uint32_t>, dim3(grid), dim3(256), lds, s, a, v);
+    else hipLaunchKernelGGL(k_eval_episodes_h<uint64_t>, dim3(grid), dim3(256), lds, s, a, v);
     HIP_TRY(hipGetLastError());
     return UAVENV_OK;
 }

@@ -1,6 +1,7 @@
 """Policy evaluation: whole episodes in one GPU launch -- greedy DQN (csrc/uavenv.hip k_eval_episodes, include/uavenv.h
-uavenv_eval_episodes; one net per UAV slot and APF envs: k_eval_episodes_slots, uavenv_eval_episodes_slots) and the continuous
-SAC actor, APF on or off (k_eval_episodes_sac, uavenv_eval_episodes_sac).
+uavenv_eval_episodes; an f16-MFMA learner: k_eval_episodes_h, uavenv_eval_episodes_f16; one net per UAV slot and APF envs:
+k_eval_episodes_slots, uavenv_eval_episodes_slots) and the continuous SAC actor, APF on or off (k_eval_episodes_sac,
+uavenv_eval_episodes_sac).
 
 The reference meant to have this (Envs/PathPlan_City.py:349-351 Evaluation_Action, :543-552 run_XML_scene / Load_Scene_FromXML)
 and acts greedily when Is_Train == 0 (Trainer/DuelingDQN_Trainer.py:90).  Episode e flies scenario row (first + e) mod m of a
@@ -92,12 +93,14 @@ def _check_scenarios(scenarios, K):
 
 def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int = 0, seed: int = 0, eps: float = 0.0,
                     max_steps: int = 0, v0=None, trajectory_steps: int = 0, max_workgroups: int = 0) -> EvalResult:
-    """n_episodes greedy episodes of learner.q_local (a FusedDQNLearner on the f32 MFMA) on env (a VecPathPlanEnv, APF on or off).
+    """n_episodes greedy episodes of learner.q_local (a FusedDQNLearner) on env (a VecPathPlanEnv, APF on or off).
 
     learner: one FusedDQNLearner, or a list / tuple of 1 or env.uav_per_env of them -- episode e is then flown by learner e mod U,
     as UAV slot e mod U, all of them in ONE launch (uavenv_eval_episodes_slots; max_workgroups then bounds the workgroups per
     learner).  A single learner on a non-APF env goes through uavenv_eval_episodes; a list, or an APF env, through the slots entry
-    (an APF env keeps one [K, 3] f64 sub-goal list per resident lane, 256 lanes per workgroup).
+    (an APF env keeps one [K, 3] f64 sub-goal list per resident lane, 256 lanes per workgroup).  A single learner with
+    mfma = "f16" goes through uavenv_eval_episodes_f16 -- the f16-MFMA forward it acts with, on the halves an f16 or packed env
+    feeds it -- and needs a non-APF env with f16 or packed rows; the list and APF forms take f32-MFMA learners only.
 
     scenarios: None (the env's bank) or (start_goal [m,6] f64, sub_goals [m,K,3] f64, n_sub [m] i32) device tensors, e.g.
     held_out_scenarios(env, m, seed).  v0: [n,2] raw initial V_vector per episode (default: headings from Philox(seed, e)).
@@ -117,10 +120,17 @@ def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int
             raise ValueError("evaluate_policy needs fused learners (FusedDQNLearner)")
         if len(kinds) != 1:
             raise ValueError(f"the learners must share one kind and action count (got (n_actions, dueling) = {sorted(kinds)})")
+        if any(getattr(L, "mfma", "f32") != "f32" for L in ls):
+            raise ValueError("the per-slot form (a list of learners) takes f32-MFMA nets only; evaluate an f16-MFMA learner on its own")
+    f16 = not as_list and getattr(learner, "mfma", "f32") == "f16"
     if v0 is not None and tuple(np.shape(v0)) != (n, 2):
         raise ValueError(f"v0 must be [{n}, 2] (got {tuple(np.shape(v0))})")
     if as_list and len(ls) != 1 and len(ls) != env.uav_per_env:
         raise ValueError(f"one learner or uav_per_env = {env.uav_per_env} of them (got {len(ls)})")
+    if f16 and int(env.cfg.apf_enabled) == 1:
+        raise ValueError("an f16-MFMA learner is evaluated on non-APF envs only (the APF form takes f32-MFMA nets)")
+    if f16 and env.obs_code not in (_lib.OBS_F16, _lib.OBS_PACKED):
+        raise ValueError("an f16-MFMA learner is evaluated on an env with f16 or packed rows (what it acts on), not f32 rows")
     import torch
     dev = env.device
     if v0 is not None:
@@ -147,7 +157,9 @@ def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int
     a.traj_pos = None if pos is None else pos.data_ptr()
     a.traj_act = None if act is None else act.data_ptr()
     a.max_workgroups = int(max_workgroups)
-    if as_list or int(env.cfg.apf_enabled) == 1:
+    if f16:
+        _lib.check(env.lib.uavenv_eval_episodes_f16(env._h, C.byref(learner.net), C.byref(a), env._stream()), "uavenv_eval_episodes_f16")
+    elif as_list or int(env.cfg.apf_enabled) == 1:
         nets = (C.POINTER(_lib.UavDqnNet) * len(ls))(*[C.pointer(L.net) for L in ls])
         _lib.check(env.lib.uavenv_eval_episodes_slots(env._h, nets, len(ls), C.byref(a), env._stream()), "uavenv_eval_episodes_slots")
     else:

@@ -456,7 +456,9 @@ class PathPlan_City:
                                           max_steps=int(max_steps)).host_records()
             return [_ev.summarize(rec[j::U]) for j in range(U)]
         distinct = len({id(L) for L in learners})
-        if distinct == U or distinct == 1:             # net j flies the episodes = j (mod U), nothing else: ONE launch
+        # (f16-MFMA learners have no per-slot form: one shared by every slot flies alone, U distinct ones fly one launch each below)
+        f16 = any(getattr(L, "mfma", "f32") == "f16" for L in learners)
+        if distinct == 1 or (distinct == U and not f16):   # net j flies the episodes = j (mod U), nothing else: ONE launch
             who = learners if distinct == U and U > 1 else learners[0]
             rec = _ev.evaluate_policy(self.backend, who, n * U, scenarios=scn_u, v0=v0, seed=int(seed),
                                       max_steps=int(max_steps)).host_records()

@@ -534,6 +534,19 @@ typedef struct UavEvalArgs {
 } UavEvalArgs;
 int uavenv_eval_episodes(UavEnv *env, const UavDqnNet *net, const UavEvalArgs *args, void *stream);
 
+/* ---- the same for an f16-MFMA net (UAVENV_MFMA_F16: BASELINE configs[2]) ----------------------------------------------------------
+ * uavenv_eval_episodes with the policy an f16 learner acts with: Q(s) by the f16-MFMA forward of uavenv_dqn_act (fc1, b1 and the
+ * observation row rounded to f16, four v_mfma_f32_16x16x32_f16 per accumulator, f32 accumulation, fc2 / b2 in f32: bit-identical Q
+ * values), not the f32 master weights under the f32 forward.  The row's halves are what the env's own launches feed the net: the
+ * halves an UAVENV_OBS_F16 env stores, which are also the halves uavenv_dqn_act expands an UAVENV_OBS_PACKED row to.  Everything
+ * else -- episodes, scenario rows, the reset, v0 / the heading draw, the first-maximum action, the eps draw, the end of an episode,
+ * UavEvalArgs, UavEvalRecord, the trajectory, the grid, what is left untouched on the env -- is uavenv_eval_episodes'.
+ * Takes a non-APF env with a world whose obs_dtype is UAVENV_OBS_F16 or UAVENV_OBS_PACKED, and an f16-MFMA net of w 100, hid 64, the
+ * env's n_actions >= 2, at most 4 layer-2 outputs and a 16-byte aligned `local`.  UAVENV_EINVAL, with nothing allocated or enqueued,
+ * otherwise (an f32-MFMA net, an UAVENV_OBS_F32 env, an APF env, more than 4 outputs) and for every argument uavenv_eval_episodes
+ * refuses.  uavenv_eval_episodes and uavenv_eval_episodes_slots keep refusing f16-MFMA nets. */
+int uavenv_eval_episodes_f16(UavEnv *env, const UavDqnNet *net, const UavEvalArgs *args, void *stream);
+
 /* ---- greedy DQN evaluation with one net per UAV slot, APF on or off, in one launch ---------------------------------------------------
  * uavenv_eval_episodes for n_nets nets (n_nets = 1, or uav_per_env <= UAVENV_SAC_LOOP_MAX_SLOTS: one net per UAV slot,
  * Envs/PathPlan_City.py:59-69) and for envs with APF on as well as off.  Episode e is flown by net e mod n_nets as UAV slot

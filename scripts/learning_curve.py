@@ -6,6 +6,11 @@ The settings (envs, learner batch, replay capacity, trainer, training epsilon, r
 uniform random policy).  Held-out rows are planned on a seed the training bank never uses.  Output: one JSON document.
     python scripts/learning_curve.py [--passes 1000000] [--every 50000] [--episodes 16384] [--out profiles/learning_curve_configs1.json]
 
+--config 2: BASELINE configs[2] as `bench.py --config 3` builds it (65 536 envs, dueling + DDQN, f16 observation rows, the f16-MFMA
+learner, HotLoop), evaluated through uavenv_eval_episodes_f16: the f16 policy the learner acts with, on the halves the f16 ring
+feeds it.  Same baselines, same held-out rows.
+    python scripts/learning_curve.py --config 2 [--passes 1000000] [--every 50000] [--episodes 16384] [--out profiles/learning_curve_configs2.json]
+
 --config 3: BASELINE configs[3] as `bench.py --config 4` builds it (run_config4: 4 UAV slots x 32 768 envs, APF on with the
 velocities of default_rng(42), one fused SAC learner per slot, SACHotLoop), with a held-out evaluation of the four actors in one
 launch (uavenv_eval_episodes_sac) every --every passes, in both modes ("mean": noise 0; "sample": as get_action flies).  Every
@@ -35,11 +40,11 @@ from dqn_based_uav_3d_path_planer_amd.replay import DeviceReplayRing  # noqa: E4
 HELD_OUT_SEED = 0x4E1D_0C7                # the training bank is planned on seed 42 (+ rank): bench.py run_dqn
 
 
-def bench_settings():
-    """bench.py's defaults for the single-GPU DQN run (its argument parser, no arguments)."""
+def bench_settings(*argv_extra):
+    """bench.py's settings for the single-GPU DQN run (its argument parser: no arguments, or --config 3 for configs[2])."""
     sys.path.insert(0, ROOT)
     import bench
-    argv, sys.argv = sys.argv, ["bench.py"]
+    argv, sys.argv = sys.argv, ["bench.py", *argv_extra]
     try:
         a = bench.parse()
     finally:
@@ -172,7 +177,8 @@ def main_config3(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, default=1, choices=[1, 3], help="BASELINE configs[1] (DQN) or configs[3] (4 x SAC, APF)")
+    ap.add_argument("--config", type=int, default=1, choices=[1, 2, 3],
+                    help="BASELINE configs[1] (DQN), configs[2] (dueling DDQN, f16 rows, f16 MFMA) or configs[3] (4 x SAC, APF)")
     ap.add_argument("--passes", type=int, default=None)
     ap.add_argument("--every", type=int, default=None)
     ap.add_argument("--episodes", type=int, default=None)
@@ -183,25 +189,32 @@ def main():
     args.passes = args.passes if args.passes is not None else (40000 if c3 else 1000000)
     args.every = args.every if args.every is not None else (4000 if c3 else 50000)
     args.episodes = args.episodes if args.episodes is not None else (4096 if c3 else 16384)
-    args.out = args.out or ("profiles/learning_curve_configs3.json" if c3 else "profiles/learning_curve_configs1.json")
+    args.out = args.out or "profiles/learning_curve_configs%d.json" % args.config
     if c3:
         return main_config3(args)
-    b = bench_settings()
-    if b.trainer not in ("dqn", "ddqn", "dueling") or b.mfma != "f32":
+    c2 = args.config == 2
+    b = bench_settings("--config", "3") if c2 else bench_settings()
+    if c2 and (b.trainer != "dueling" or b.mfma != "f16" or b.obs_dtype != "f16"):
+        raise SystemExit("bench.py --config 3 is expected to be the dueling f16-MFMA learner on f16 rows")
+    if not c2 and (b.trainer not in ("dqn", "ddqn", "dueling") or b.mfma != "f32"):
         raise SystemExit("bench.py's default run is expected to be the f32 DQN family")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     bank_size = b.bank_size or max(b.envs, 4096)            # (bench.py run_dqn: the bank without rolling refresh)
-    env = make_city26_env(b.envs, bank=b.bank, bank_size=bank_size, bank_seed=42, device=dev, obs_dtype="packed")
+    env = make_city26_env(b.envs, bank=b.bank, bank_size=bank_size, bank_seed=42, device=dev,
+                          obs_dtype=torch.float16 if c2 else "packed")
     ring = DeviceReplayRing(env, b.replay, discrete=True)
     ring.reset(seed=1000)
     torch.manual_seed(42)
     net = "VAnet2" if b.trainer == "dueling" else "Qnet2"
-    learner = FusedDQNLearner({"NetWork": net, "w": "100", "hiden_dim": "64", "output": "3"}, b.trainer, device=dev)
+    learner = FusedDQNLearner({"NetWork": net, "w": "100", "hiden_dim": "64", "output": "3"}, b.trainer, device=dev, mfma=b.mfma)
     loop = HotLoop(ring, learner, b.batch, 7, eps=b.eps)
     scn = ev.held_out_scenarios(env, args.episodes, seed=HELD_OUT_SEED)
-    out = {"what": "configs[1] training (bench.py defaults) with greedy held-out evaluations", "settings": {
-               "envs": b.envs, "batch": b.batch, "replay": b.replay, "trainer": b.trainer, "train_eps": b.eps, "bank": b.bank,
+    what = ("configs[2] training (bench.py --config 3: dueling DDQN, f16 rows, f16 MFMA) with greedy held-out evaluations of the "
+            "f16 policy (uavenv_eval_episodes_f16)") if c2 else "configs[1] training (bench.py defaults) with greedy held-out evaluations"
+    out = {"what": what, "settings": {
+               "envs": b.envs, "batch": b.batch, "replay": b.replay, "trainer": b.trainer, "mfma": b.mfma, "obs_dtype": b.obs_dtype,
+               "train_eps": b.eps, "bank": b.bank,
                "bank_size": bank_size, "passes": args.passes, "every": args.every, "eval_episodes": args.episodes,
                "eval_max_steps": args.max_steps, "held_out_seed": HELD_OUT_SEED},
            "baselines": {"untrained_greedy": evaluation(env, learner, scn, args.episodes, args.max_steps),

@@ -22,6 +22,13 @@ slot's rows (gathered to a contiguous block, the actions scattered back) + uaven
 (k_apf_adjust + k_step).  Launches only, device events, a warm-up of both forms, then the two forms alternating in the same process,
 median of the repeats; every record checked equal before a time is taken.
     python scripts/time_eval.py --slots [--reps 5] [--max-steps 600] [--out profiles/eval_slots_times.json]
+
+--f16: greedy evaluation of an f16-MFMA net (uavenv_eval_episodes_f16; an untrained dueling VAnet2, BASELINE configs[2]'s shape) on
+an f16 env and on a packed env, against set_state + per step uavenv_dqn_act (the env's obs_dtype, eps = -1) + uavenv_step with
+SKIP_DONE; on the f16 env, where uavenv_step_policy takes the shape (at most 65 536 agents, its one-wavefront form), that one launch
+per step is timed as well.  Launches only, device events, a warm-up of every form, then the forms alternating in the same process,
+median of the repeats; every record checked equal before a time is taken.
+    python scripts/time_eval.py --f16 [--reps 5] [--max-steps 600] [--out profiles/eval_f16_times.json]
 """
 from __future__ import annotations
 
@@ -114,6 +121,147 @@ class Composition:
         b.record()
         b.synchronize()
         return a.elapsed_time(b)
+
+
+class F16Composition(Composition):
+    """Composition for an f16-MFMA net on an env of f16 or packed rows: uavenv_dqn_act + uavenv_step per step, or (policy = True, f16
+    rows, <= 65 536 agents) uavenv_step_policy in its one-wavefront form."""
+
+    def __init__(self, L, scn, n, v0, obs, max_steps):
+        self.L, self.n, self.max_steps, self.policy = L, n, max_steps, False
+        sg, sub, ns = (x.cpu().numpy() for x in scn)
+        rows = np.arange(n) % len(sg)
+        self.env = make_city26_env(n, obs_dtype=torch.float16 if obs == "f16" else "packed")
+        self.kin = np.concatenate([sg[rows, :3], v0, sg[rows, 3:]], 1)
+        self.nsub = ns[rows]
+        self.sub = sub[rows]
+        d = self.env.device
+        self.obs = [self.env.new_obs(), self.env.new_obs()]
+        self.act = torch.zeros(n, dtype=torch.int32, device=d)
+        self.r64 = torch.zeros(n, dtype=torch.float64, device=d)
+        self.en = torch.zeros(n, dtype=torch.float64, device=d)
+        self.info = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.adone = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.valid = torch.zeros(n, dtype=torch.uint8, device=d)
+
+    def step(self, t):
+        e, o0, o1 = self.env, self.obs[t % 2], self.obs[(t + 1) % 2]
+        if self.policy:
+            flags = _lib.STEP_SKIP_DONE | (_lib.STEP_ONE_WAVE if self.n <= POLICY_MAX else 0)
+            rc = e.lib.uavenv_step_policy(e._h, C.byref(self.L.net), o0.data_ptr(), -1.0, 5, t, self.act.data_ptr(), o1.data_ptr(),
+                                          self.r64.data_ptr(), None, None, self.adone.data_ptr(), self.info.data_ptr(),
+                                          self.valid.data_ptr(), self.en.data_ptr(), None, flags, e._stream())
+            _lib.check(rc, "uavenv_step_policy")
+        else:
+            self.L.act(o0, -1.0, 5, t, index_out=self.act)
+            _lib.check(e.lib.uavenv_step(e._h, self.act.data_ptr(), _lib.ACT_INDEX_I32, o1.data_ptr(), self.r64.data_ptr(), None,
+                                         None, self.adone.data_ptr(), self.info.data_ptr(), self.valid.data_ptr(),
+                                         self.en.data_ptr(), None, _lib.STEP_SKIP_DONE, e._stream()), "uavenv_step")
+
+    def records(self):
+        """Composition.records with the truncation at max_steps / the natural bound."""
+        self.reset()
+        n, d = self.n, self.env.device
+        ret = torch.zeros(n, dtype=torch.float64, device=d)
+        energy = torch.zeros(n, dtype=torch.float64, device=d)
+        steps = torch.zeros(n, dtype=torch.int32, device=d)
+        outcome = torch.zeros(n, dtype=torch.uint8, device=d)
+        cap = torch.as_tensor(self.nsub.astype(np.int64) * self.env.cfg.max_step + 1, device=d)
+        if self.max_steps > 0:
+            cap = torch.clamp(cap, max=self.max_steps)
+        t = 0
+        while True:
+            self.step(t)
+            live = (self.valid == 1) & (outcome == 0)
+            ret += torch.where(live, self.r64, torch.zeros_like(self.r64))
+            energy += torch.where(live, self.en, torch.zeros_like(self.en))
+            steps += live.to(torch.int32)
+            fin = live & (self.adone == 1)
+            outcome[fin] = torch.where(self.info[fin] == _lib.INFO_LOSE, _lib.EVAL_LOSE, _lib.EVAL_SUCCESS).to(torch.uint8)
+            outcome[live & (outcome == 0) & (steps >= cap)] = _lib.EVAL_TRUNCATED
+            t += 1
+            if t % 16 == 0 and not bool((outcome == 0).any()):
+                break
+        return dict(ret=ret.cpu().numpy(), energy=energy.cpu().numpy(), steps=steps.cpu().numpy(), outcome=outcome.cpu().numpy()), \
+            int(steps.max())
+
+
+def main_f16(args):
+    torch.cuda.set_device(0)
+    torch.manual_seed(0)
+    L = FusedDQNLearner(dict(PARAM, NetWork="VAnet2"), "dueling", device="cuda:0", mfma="f16")
+    probe = make_city26_env(64, obs_dtype="packed")
+    scn = ev.held_out_scenarios(probe, 16384, seed=0xE7A1)
+    probe.close()
+    out = {"what": "greedy evaluation of an untrained f16-MFMA dueling VAnet2 in one launch (uavenv_eval_episodes_f16) on held-out city26 "
+                   "episodes against uavenv_dqn_act + uavenv_step per step on an env of the same rows, and on f16 rows up to 65 536 agents "
+                   "against uavenv_step_policy per step.  Launches only, device events, a warm-up, the forms alternating, median of %d"
+                   % args.reps,
+           "max_steps": args.max_steps, "sizes": []}
+
+    def same(rec, ref):
+        return (np.array_equal(rec["ret"], ref["ret"]) and np.array_equal(rec["energy"], ref["energy"]) and
+                np.array_equal(rec["steps"], ref["steps"]) and np.array_equal(rec["outcome"], ref["outcome"]))
+
+    for obs in ("f16", "packed"):
+        for n in (int(x) for x in args.sizes.split(",")):
+            v0 = np.random.default_rng(n).uniform(0, 2 * np.pi, n)
+            v0 = np.stack([np.cos(v0), np.sin(v0)], 1)
+            comp = F16Composition(L, scn, n, v0, obs, args.max_steps)
+            kw = dict(scenarios=scn, v0=v0, max_steps=args.max_steps)
+            res = ev.evaluate_policy(comp.env, L, n, **kw)
+            rec = res.host_records()
+            ref, n_steps = comp.records()
+            with_policy = obs == "f16" and n <= 65536 and n % 2 == 0
+            if with_policy:
+                comp.policy = True
+                try:
+                    ref_p, n_steps_p = comp.records()
+                except _lib.UavEnvError:             # uavenv_step_policy does not take this shape (EINVAL, nothing enqueued)
+                    with_policy = False
+                comp.policy = False
+            if not same(rec, ref) or (with_policy and not (same(rec, ref_p) and n_steps_p == n_steps)):
+                raise SystemExit(f"{obs} rows, n = {n}: the kernel's records differ from the composition's; no time reported")
+            agent_steps = int(rec["steps"].sum())
+
+            def timed_eval():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                ev.evaluate_policy(comp.env, L, n, **kw)
+                b.record()
+                b.synchronize()
+                return a.elapsed_time(b)
+
+            def timed_comp(policy, steps):
+                comp.policy = policy
+                return comp.timed(steps)
+
+            timed_eval()
+            timed_comp(False, min(n_steps, 32))
+            if with_policy:
+                timed_comp(True, min(n_steps, 32))
+            t_eval, t_comp, t_pol = [], [], []
+            for _ in range(args.reps):               # the forms alternating
+                t_eval.append(timed_eval())
+                t_comp.append(timed_comp(False, n_steps))
+                if with_policy:
+                    t_pol.append(timed_comp(True, n_steps))
+            me, mc = float(np.median(t_eval)), float(np.median(t_comp))
+            row = {"obs": obs, "episodes": n, "agent_steps": agent_steps, "steps_longest": n_steps, "records_equal": True,
+                   "eval_ms": me, "eval_ms_all": t_eval, "comp_ms": mc, "comp_ms_all": t_comp, "comp_form": "dqn_act + step",
+                   "eval_agent_steps_per_s": agent_steps / (me * 1e-3), "comp_agent_steps_per_s": agent_steps / (mc * 1e-3),
+                   "eval_us_per_episode": me * 1e3 / n, "comp_us_per_episode": mc * 1e3 / n, "speedup": mc / me}
+            if with_policy:
+                mp = float(np.median(t_pol))
+                row.update({"step_policy_ms": mp, "step_policy_ms_all": t_pol, "speedup_vs_step_policy": mp / me})
+            row["summary"] = res.summary()
+            print(json.dumps({k: v for k, v in row.items() if not k.endswith("_all") and k != "summary"}), flush=True)
+            out["sizes"].append(row)
+            comp.env.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
 
 
 SAC_PARAM = {"actor": {"NetWork": "PolicyNetContinuous_SAC", "w": "100", "action_bound": "1", "hiden_dim": "64", "output": "2",
@@ -419,10 +567,14 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--sac", action="store_true", help="time uavenv_eval_episodes_sac (APF off and on) instead")
-    ap.add_argument("--max-steps", type=int, default=600, help="--sac / --slots: truncate episodes (0: natural ends)")
+    ap.add_argument("--max-steps", type=int, default=600, help="--sac / --slots / --f16: truncate episodes (0: natural ends)")
     ap.add_argument("--slots", action="store_true", help="time uavenv_eval_episodes_slots (four DQN nets, APF off and on) instead")
+    ap.add_argument("--f16", action="store_true", help="time uavenv_eval_episodes_f16 (an f16-MFMA net on f16 and packed rows) instead")
     ap.add_argument("--once", type=int, default=0, help="--slots: no timing, one launch per APF setting at this many episodes per net")
     args = ap.parse_args()
+    if args.f16:
+        args.out = args.out or "profiles/eval_f16_times.json"
+        return main_f16(args)
     if args.out is None:
         args.out = "profiles/eval_slots_times.json" if args.slots else "profiles/eval_sac_times.json" if args.sac else "profiles/eval_times.json"
     if args.slots:
