@@ -19,6 +19,21 @@ HEADERS = ["uavenv_device.hpp", "qnet_device.hpp", "dqn_internal.hpp", "dqn_slot
 # separate multiplies and adds (no FMA fusion); see csrc/uavenv_device.hpp.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-Wno-unused-value", "-ldl"]
+# Kernel-argument preload (gfx950): a wavefront starts with the leading dwords of its kernel's argument block in scalar registers
+# (as many as the free user SGPRs hold: 14 here) instead of fetching them with its first instructions -- for the translation unit
+# of k_dqn_reduce_adam, whose argument order is made for it.  The flag is per translation unit: every kernel
+# of learner.hip with flat leading arguments gets them preloaded; a struct passed by value never is (the gradient and step kernels
+# take one, and stay as they were).  This hipcc's front end ignores a per-parameter `inreg`.
+# UAVENV_NO_KERNARG_PRELOAD=1 builds without the flag: A/B only.
+PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+PRELOAD_SOURCES = ("learner.hip",)
+
+
+def unit_flags(src: str) -> list:
+    """The flags of one translation unit beyond FLAGS."""
+    if src in PRELOAD_SOURCES and not os.environ.get("UAVENV_NO_KERNARG_PRELOAD"):
+        return list(PRELOAD_FLAGS)
+    return []
 
 
 def _hipcc() -> str:
@@ -58,6 +73,7 @@ def _build_locked(verbose: bool, force: bool = False) -> str:
     from concurrent.futures import ThreadPoolExecutor
     extra = ["-DUAVENV_PHASE_PROFILE"] if os.environ.get("UAVENV_PHASE_PROFILE") else []   # diagnostics build
     extra += os.environ.get("UAVENV_EXTRA_FLAGS", "").split()                              # A/B experiments
+    extra += ["-DUAVENV_NO_KERNARG_PRELOAD"] if os.environ.get("UAVENV_NO_KERNARG_PRELOAD") else []   # (names the object directory too)
     hipcc = _hipcc()
     cflags = [f for f in FLAGS if f not in ("-shared", "-ldl")] + extra
     objdir = os.path.join(PKG_DIR, "build", "obj" + ("_" + "_".join(extra).replace("-", "").replace("=", "") if extra else ""))
@@ -70,7 +86,7 @@ def _build_locked(verbose: bool, force: bool = False) -> str:
         obj = os.path.join(objdir, src + ".o")
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(path), hdr_t):
             return obj, None
-        cmd = [hipcc] + cflags + ["-c", path, "-o", obj + ".tmp.%d" % os.getpid()]
+        cmd = [hipcc] + cflags + unit_flags(src) + ["-c", path, "-o", obj + ".tmp.%d" % os.getpid()]
         if verbose:
             print(" ".join(cmd))
         res = subprocess.run(cmd, capture_output=True, text=True)

@@ -1487,10 +1487,11 @@ constexpr size_t kGrad2Lds = (size_t)(4 * kTileF + kTile * kLh + kTile * kMaxOut
 // thread's loads (<= 8 rows of 16 bytes per 256 rows) independent and in flight together -- one memory round trip (a
 // dependent walk over the rows was 8 round trips: 6 us for 256 rows).  Returns the sum of column blockIdx.x * 32 + tid
 // to threads tid < 32 (others: 0).  `c_out`: this thread's share of the valid-count column.
-__device__ __forceinline__ float reduce_columns(const float *__restrict__ partials, int nblk, int P, int stride, float &c_out)
+//
+// In two halves, so that k_dqn_reduce_adam can put its gate between them: reduce_columns_load is every global load and the sums a
+// thread keeps in registers (harmless on a pass that is gated off), reduce_columns_sum the LDS reduction behind it.
+__device__ __forceinline__ floatx4 reduce_columns_load(const float *__restrict__ partials, int nblk, int P, int stride, float &c_out)
 {
-    __shared__ float red[32][33];
-    __shared__ float red2[8][33];
     const int tid = (int)threadIdx.x;
     const int cg = tid & 7, rg = tid >> 3;                       // column group (4 columns), row group
     const int p4 = (int)blockIdx.x * 32 + cg * 4;                // first of this thread's four columns (stride % 4 == 0)
@@ -1516,6 +1517,15 @@ __device__ __forceinline__ float reduce_columns(const float *__restrict__ partia
         }
     }
     c_out = c;
+    return acc;
+}
+
+__device__ __forceinline__ float reduce_columns_sum(const floatx4 &acc)
+{
+    __shared__ float red[32][33];
+    __shared__ float red2[8][33];
+    const int tid = (int)threadIdx.x;
+    const int cg = tid & 7, rg = tid >> 3;
 #pragma unroll
     for (int e = 0; e < 4; ++e) red[rg][cg * 4 + e] = acc[e];
     __syncthreads();
@@ -1530,6 +1540,11 @@ __device__ __forceinline__ float reduce_columns(const float *__restrict__ partia
         for (int k = 0; k < 8; ++k) t += red2[k][tid];
     }
     return t;
+}
+
+__device__ __forceinline__ float reduce_columns(const float *__restrict__ partials, int nblk, int P, int stride, float &c_out)
+{
+    return reduce_columns_sum(reduce_columns_load(partials, nblk, P, stride, c_out));
 }
 
 // raw[p] = sum_b partial[b][p] for p in [0, P+2): gradient sums, loss sum, valid count (the multi-GPU all-reduce payload).
@@ -1571,12 +1586,16 @@ __global__ void k_dqn_adam(float *__restrict__ local, float *__restrict__ target
 
 // Single-GPU fast path: k_dqn_reduce + k_dqn_adam in one launch (each workgroup owns 32 parameters end to end; the
 // valid count is re-derived per workgroup from the count cells, one load per thread).
+// The order of the arguments is the order of need: the first 14 dwords -- what a wavefront has in scalar registers when it starts
+// (kernel-argument preload, _build.py: PRELOAD_FLAGS) -- are exactly the operands of the kernel's loads, the gate word among them
+// (go_value fills the alignment hole behind stride); target and everything else is first used behind those loads' round trip.
 __global__ void __launch_bounds__(256) k_dqn_reduce_adam(const float *__restrict__ partials, int nblk, int P, int stride,
-                                                         float *__restrict__ local, float *__restrict__ target,
-                                                         float *__restrict__ m, float *__restrict__ v, float lr,
+                                                         uint32_t go_value, float *__restrict__ local,
+                                                         const uint32_t *__restrict__ go_word, float *__restrict__ m,
+                                                         float *__restrict__ v, float *__restrict__ target, float lr,
                                                          float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
                                                          int hard_update, float *__restrict__ loss, float *__restrict__ raw,
-                                                         const uint32_t *__restrict__ go_word, uint32_t go_value, float *__restrict__ img)
+                                                         float *__restrict__ img)
 {
 #include "reduce_adam_body.inc"
 }
@@ -2100,8 +2119,8 @@ int uavenv_dqn_reduce_adam_img(const UavDqnNet *net, const float *partials, int3
     const float bc1 = 1.0f - powf(beta1, (float)step_t);
     const float bc2 = 1.0f - powf(beta2, (float)step_t);
     hipLaunchKernelGGL(k_dqn_reduce_adam, dim3((P + 2 + 31) / 32), dim3(256), 0, (hipStream_t)stream, partials, n_partials,
-                       P, uavenv_dqn_partial_stride(net), net->local, net->target, net->m, net->v, lr, beta1, beta2, eps, bc1, sqrtf(bc2), hard_update,
-                       loss_out, raw_out, go_word_dev, go_value, image_dev);
+                       P, uavenv_dqn_partial_stride(net), go_value, net->local, go_word_dev, net->m, net->v, net->target, lr, beta1, beta2, eps,
+                       bc1, sqrtf(bc2), hard_update, loss_out, raw_out, image_dev);
     return hipGetLastError() == hipSuccess ? UAVENV_OK : UAVENV_EHIP;
 }
 

@@ -3,6 +3,8 @@
 
     python scripts/isa_account.py <tag>                      -> profiles/isa_account_<tag>.txt
     python scripts/isa_account.py <tag> --compare OTHER_CSRC -> profiles/isa_compare_<tag>.txt   (two trees, kernel by kernel)
+    python scripts/isa_account.py <tag> --preload OTHER_CSRC -> profiles/<tag>.txt   (kernel-argument preload length, registers, spills,
+                                                                 scratch and segment s0 of the hot loop's kernels in two trees)
 
 Compiles csrc/learner.hip device-only for gfx950 with _build.FLAGS (minus -shared / -ldl) plus -gline-tables-only, disassembles
 it with source lines (llvm-objdump -d -l) and writes, for the gradient, reduce and acting kernels listed in KERNELS:
@@ -90,10 +92,13 @@ def tool(name: str) -> str:
     return name
 
 
-def compile_device(src: str, out: str, lines: bool) -> None:
+def compile_device(src: str, out: str, lines: bool, unit_flags: bool = True, asm: bool = False) -> None:
+    """unit_flags: with _build.unit_flags of the file (kernel-argument preload); False builds a tree from before them as it was built"""
     flags = [f for f in _build.FLAGS if f not in ("-shared", "-ldl")]
+    if unit_flags:
+        flags += _build.unit_flags(os.path.basename(src))
     cmd = [_build._hipcc()] + flags + (["-gline-tables-only"] if lines else []) + \
-          ["--cuda-device-only", "--no-gpu-bundle-output", "-c", src, "-o", out]
+          ["--cuda-device-only", "--no-gpu-bundle-output", "-S" if asm else "-c", src, "-o", out]
     subprocess.run(cmd, check=True)
 
 
@@ -265,7 +270,7 @@ def compare(other_csrc: str, this_csrc: str, diff_lines: int, files) -> tuple:
         def build(job):
             side, csrc, f = job
             obj = os.path.join(td, "%s_%s.o" % (f, side))
-            compile_device(os.path.join(csrc, f + ".hip"), obj, False)
+            compile_device(os.path.join(csrc, f + ".hip"), obj, False, tree_has_unit_flags(csrc))
             return (side, f), (disassemble(obj, False), descriptors(obj))
         with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
             built = dict(ex.map(build, [(side, csrc, f) for side, csrc in (("a", other_csrc), ("b", this_csrc)) for f in files]))
@@ -303,6 +308,46 @@ def compare(other_csrc: str, this_csrc: str, diff_lines: int, files) -> tuple:
     return L, ok
 
 
+PRELOAD_KERNELS = [("uavenv", "k_step_coop<unsigned int, false, 2, true, true, true>"), ("learner", "k_dqn_grad_packed8<true>"),
+                   ("learner", "k_dqn_reduce_adam"), ("learner", "k_dqn_reduce_adam_slots")]
+
+
+def tree_has_unit_flags(csrc: str) -> bool:
+    """does the tree that holds `csrc` build with per-unit flags (its _build.py, next to csrc, defines unit_flags)?"""
+    b = os.path.join(csrc, "..", "_build.py")
+    return os.path.exists(b) and "def unit_flags" in open(b).read()
+
+
+def preload_lengths(asm: str, names: dict) -> dict:
+    """{short kernel name: .amdhsa_user_sgpr_kernarg_preload_length} of an assembly listing (the kernel descriptor's field);
+    names: demangle_map of the same file's object"""
+    text = open(asm).read()
+    found = re.findall(r"\.amdhsa_kernel (\S+)\n(?:.*\n)*?\s+\.amdhsa_user_sgpr_kernarg_preload_length (\d+)", text)
+    return {short_name(names.get(sym, sym)): int(n) for sym, n in found}
+
+
+def preload_report(other_csrc: str, this_csrc: str) -> list:
+    """The three hot-loop kernels in a tree from before kernel-argument preload (built without unit flags) and in this tree: the
+    descriptor's preload length, registers, spills, scratch, and the instruction count of segment s0 (up to the first barrier)"""
+    L = ["  %-58s %-6s %8s %5s %5s %12s %8s %7s %6s" % ("kernel", "tree", "preload", "vgpr", "sgpr", "spills v/s", "scratch", "total", "s0")]
+    with tempfile.TemporaryDirectory() as td:
+        for f in sorted(set(f for f, _ in PRELOAD_KERNELS)):
+            for side, csrc, uf in (("other", other_csrc, tree_has_unit_flags(other_csrc)), ("this", this_csrc, True)):
+                obj, asm = os.path.join(td, "%s_%s.o" % (f, side)), os.path.join(td, "%s_%s.s" % (f, side))
+                compile_device(os.path.join(csrc, f + ".hip"), obj, False, uf)
+                compile_device(os.path.join(csrc, f + ".hip"), asm, False, uf, asm=True)
+                dis, desc, pre = disassemble(obj, False), descriptors(obj), preload_lengths(asm, demangle_map(obj))
+                for ff, k in PRELOAD_KERNELS:
+                    if ff != f:
+                        continue
+                    ins, d = dis[k], desc[k]
+                    bars = [i for i, (m, _, _) in enumerate(ins) if classify(m) == "barrier"]
+                    L.append("  %-58s %-6s %8d %5d %5d %12s %8d %7d %6d" % (
+                        k, side, pre[k], d["vgpr"], d["sgpr"], "%d / %d" % (d["vgpr_spills"], d["sgpr_spills"]), d["scratch"], len(ins),
+                        bars[0] if bars else len(ins)))
+    return L
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("tag")
@@ -314,7 +359,16 @@ def main() -> int:
     ap.add_argument("--csrc", default=_build.CSRC, help="directory holding learner.hip (default: this tree's csrc)")
     ap.add_argument("--out", default=None, help="output file (default profiles/isa_account_<tag>.txt)")
     ap.add_argument("--check-lines", action="store_true", help="also build without -gline-tables-only and compare the counts")
+    ap.add_argument("--preload", metavar="CSRC", default=None,
+                    help="kernel-argument preload report of the three hot-loop kernels against the csrc directory of a tree from before "
+                         "it; writes profiles/<tag>.txt")
     args = ap.parse_args()
+    if args.preload:
+        out = args.out or os.path.join(ROOT, "profiles", "%s.txt" % args.tag)
+        with open(out, "w") as f:
+            f.write("\n".join(preload_report(args.preload, args.csrc)) + "\n")
+        print(out)
+        return 0
     if args.compare:
         L, ok = compare(args.compare, args.csrc, args.diff_lines, args.files or COMPARE_FILES)
         flags = " ".join(f for f in _build.FLAGS if f not in ("-shared", "-ldl"))
