@@ -1632,18 +1632,31 @@ __global__ void k_get_state(StepArgs a, int first, int count, double *__restrict
 // is fwd_strip_split + w2_load / q_strip as there (same operands in the same K positions, same MFMA order: the same Q values), and
 // lane 16 st + r keeps strip st's result.  The forward runs wave-uniformly every iteration; idle lanes feed a zero row.
 // ------------------------------------------------------------------------------------------------
-struct EvalArgs {
-    const float *img;                  // q_local's layer 1 in the split form (uavenv_dqn_split_image)
-    const float *local;                // q_local's flat block (fc2 / b2 are read from it)
+// The four episode kernels (k_eval_episodes, _h, _sac, _slots) differ in their staging prelude, their first-episode formula and
+// their forward; everything else of the loop is ONE text, the device functions below:
+//   eval_obs_row (all four)  eval_stage_w2 (DQN: plain, _h, _slots)  eval_forward_f32 (plain, _sac, _slots; _h has its own strip loop)
+//   eval_dqn_action (DQN)    eval_step, eval_episode_end, eval_install, eval_store_record (all four)
+// The trajectory's action store stays in each kernel (int8 or float2), between eval_step and eval_episode_end, which moves L.e.
+// ------------------------------------------------------------------------------------------------
+// the per-run fields of every evaluation kernel's argument block (EvalArgs, SacEvalArgs, SlotsEvalArgs embed one as `run`)
+struct EvalRun {
     const double *v0;                  // nullable [n][2]
     uint4 *rec;                        // [n] x 64 bytes (UavEvalRecord)
     double *traj_pos;                  // nullable [n][traj_steps + 1][3]
-    int8_t *traj_act;                  // nullable [n][traj_steps]
     uint64_t seed;
+    int32_t n, first, max_steps, traj_steps;
+    int32_t lanes;                     // of the whole grid = a lane's episode stride
+    int32_t img_off, w2_off, slot_off, slot_bytes;   // LDS byte offsets: layer 1, the layer-2 block (+ biases), per-wave slots
+};
+
+// (the member order is measured: with img / local ahead of traj_act k_eval_episodes_h spilt more scalars and ran 2-3 % slower)
+struct EvalArgs {
+    EvalRun run;
+    int8_t *traj_act;                  // nullable [n][traj_steps]
+    const float *img;                  // q_local's layer 1 in the split form (uavenv_dqn_split_image)
+    const float *local;                // q_local's flat block (fc2 / b2 are read from it)
     float eps;
-    int32_t n, first, max_steps, traj_steps, lanes;
     int32_t n2, dueling;
-    int32_t img_off, w2_off, slot_off, slot_bytes;   // LDS byte offsets: image, fc2 (+ b2), per-wave slots
 };
 
 struct EvalLane {
@@ -1652,9 +1665,7 @@ struct EvalLane {
     double ret, energy, v0x, v0y;
 };
 
-// (V: EvalArgs or SacEvalArgs -- the two evaluation kernels share the record, the installation and the episode's end)
-template <typename V>
-__device__ __forceinline__ void eval_store_record(const V &v, int e, const Agent &g, const EvalLane &L, int outcome, int slot)
+__device__ __forceinline__ void eval_store_record(const EvalRun &v, int e, const Agent &g, const EvalLane &L, int outcome, int slot)
 {
     uint4 *dst = v.rec + (size_t)e * 4;
     const unsigned long long r = (unsigned long long)__double_as_longlong(L.ret), t = (unsigned long long)__double_as_longlong(g.total);
@@ -1669,8 +1680,8 @@ __device__ __forceinline__ void eval_store_record(const V &v, int e, const Agent
 
 // the first episode at or after L.e whose scenario row is valid: UAV.reset() into `g` (invalid rows get their record here).
 // APF: the scenario's sub-goal list is copied into list `li` of a.st.sub (the evaluation's own workspace, one list per resident lane).
-template <bool APF = false, typename V>
-__device__ __forceinline__ void eval_install(const StepArgs &a, const V &v, Agent &g, EvalLane &L, int li = 0)
+template <bool APF = false>
+__device__ __forceinline__ void eval_install(const StepArgs &a, const EvalRun &v, Agent &g, EvalLane &L, int li = 0)
 {
     int row = 0;
     while (L.e < v.n) {
@@ -1715,25 +1726,139 @@ __device__ __forceinline__ void eval_install(const StepArgs &a, const V &v, Agen
     }
 }
 
+// state_PathPlan of the lane's current state as a packed row (store_obs_row_packed's layout) in registers; wave-collective
+// (obs_bits_queued).  An idle lane gets a zero row, whose result is discarded.
+template <typename MaskT>
+__device__ __forceinline__ uavq::PRow eval_obs_row(const WorldLds<MaskT> &w, ObsWaveLds *Q, const Agent &g, bool have)
+{
+    const ObsBits bits = obs_bits_queued(w, Q, g.o.px, g.o.py, g.o.pz, have);
+    const ObsScalars sc = obs_scalars(g.o, g.head);
+    uavq::PRow R;
+    ctile_mask_words(bits, R.m0, R.m1, R.m2);
+#pragma unroll
+    for (int k = 0; k < 11; ++k) R.sc[k] = sc.f[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) R.sg[k] = sc.f[11 + k];
+    if (!have) {
+        R.m0 = R.m1 = R.m2 = 0u;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) R.sc[k] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) R.sg[k] = 0.0f;
+    }
+    return R;
+}
+
+// fc2 ([16][64]) and b2 ([16]) of a DQN net into LDS through registers, by the workgroup's 256 threads
+__device__ __forceinline__ void eval_stage_w2(float *W2, float *b2, const uavq::NetDev &nl, int n2, int tid)
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (tid + 256 * k < n2 * uavq::kHid) W2[tid + 256 * k] = nl.W2[tid + 256 * k];
+    if (tid < n2) b2[tid] = nl.b2[tid];
+}
+
+// The f32 forward of the wavefront's 64 rows (k_dqn_act_packed's, k_sac_act's): the rows go through the wave slot, which the
+// observation queue had before; strip st (rows of lanes 16 st .. 16 st + 15) is fwd_strip_split + w2_load / q_strip -- the same
+// operands in the same K positions, the same MFMA order -- and lane 16 st + r keeps strip st's result.  Wave-uniform.
+__device__ __forceinline__ void eval_forward_f32(const uavq::W1Split &W1, const float *W2, const float *b2, uint32_t *rows,
+                                                 const uavq::PRow &R, int lane, int n2, int n_actions, int dueling, float (&q)[4])
+{
+    const int r16 = lane & 15, grp = lane >> 4;
+    wave_lds_sync();                                                 // (the queue's last reads are done: the rows take its bytes)
+    uavq::prow_store_lds(rows + lane * kPackedDwords, R);
+    wave_lds_sync();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = 0.0f;
+#pragma unroll 1
+    for (int st = 0; st < 4; ++st) {
+        uavq::PRow Rs;
+        uavq::prow_load(Rs, rows + (16 * st + r16) * kPackedDwords);
+        uavq::floatx4 h[4];
+        uavq::fwd_strip_split<false>(W1, Rs, h);
+        uavq::W2Frag<4> F;
+        uavq::w2_load<4>(F, W2, b2, n2);
+        float qs[4];
+        uavq::q_strip<4>(h, F, n2, n_actions, dueling, qs);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = grp == st ? qs[k] : q[k];
+    }
+    wave_lds_sync();                                                 // the rows are read: the next iteration's queue may take the bytes
+}
+
+// The action of a DQN lane: the acting kernels' greedy branch (first maximum, strict >); eps > 0: a uniform action where the
+// 24-bit draw of Philox (seed; e, step, 0, 0xe75f) is < eps.
+__device__ __forceinline__ int eval_dqn_action(const float (&q)[4], int A, float eps, uint64_t seed, int e, int step)
+{
+    int act = 0;
+    float bq = q[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+        if (k < A && q[k] > bq) { bq = q[k]; act = k; }
+    if (eps > 0.0f) {
+        const uint4 rn = philox4x32_10(make_uint4((uint32_t)e, (uint32_t)step, 0u, 0xe75fu), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+        const float u = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
+        if (u < eps) act = (int)(((uint64_t)rn.y * (uint64_t)A) >> 32);
+    }
+    return act;
+}
+
+// update_PathPlan (UAV.py:397-513, step_agent's pieces) of episode L.e with the decoded action a0, and the episode's accounting.
+// The sub-goal list is the resident lane's own with APF (`li`, as eval_install), else the episode's scenario row; j = L.e mod U is
+// the UAV slot.  Stores the trajectory position; true when the step lies inside the trajectory window (the kernel then stores its
+// action).  (The list index is chosen here, not by the caller: with the caller's copy of L.e k_eval_episodes_h took one AGPR less.)
+template <typename MaskT, bool APF>
+__device__ __forceinline__ bool eval_step(const StepArgs &a, const WorldLds<MaskT> &w, const EvalRun &v, double a0, int j, Agent &g,
+                                          EvalLane &L, int &info, int li = 0)
+{
+    PreStep P;
+    step_pre(a, a0, g, P);
+    if (P.moved) g.head = angle_of<true>(g.o.vx, g.o.vy);           // :423
+    double r = 0.0;
+    int ret_done = 0;
+    bool head_set = false;
+    info = UAVENV_INFO_NORMAL;
+    step_post<MaskT, APF, true>(a, w, APF ? li : L.e, a0, g, P, r, ret_done, info, head_set);
+    g.o.n_rem = g.n_total - g.sub_idx;
+    L.steps += 1;
+    L.ret += r;
+    L.energy += fly_power(a.pw, g.o.V, j);
+    // a move always changes x or y (|V_vector| = Max_V > 0): the position is back where it was only after :425-428
+    if (P.moved && g.o.px == P.ox && g.o.py == P.oy && g.o.pz == P.oz) L.collisions += 1;
+    const bool in_window = L.steps <= v.traj_steps;
+    if (in_window) {
+        double *p = v.traj_pos + ((size_t)L.e * (v.traj_steps + 1) + L.steps) * 3;
+        p[0] = g.o.px; p[1] = g.o.py; p[2] = g.o.pz;
+    }
+    return in_window;
+}
+
+// The end of an episode: done, max_steps or the natural bound -> the record, then the lane's next episode.  True when the lane
+// has to install it (eval_install at the loop's top).
+__device__ __forceinline__ bool eval_episode_end(const EvalRun &v, const Agent &g, EvalLane &L, int info, int j)
+{
+    const bool trunc = (v.max_steps > 0 && L.steps >= v.max_steps) || L.steps >= L.cap;
+    if (!g.done && !trunc) return false;
+    const int outcome = g.done ? (info == UAVENV_INFO_LOSE ? UAVENV_EVAL_LOSE : UAVENV_EVAL_SUCCESS) : UAVENV_EVAL_TRUNCATED;
+    eval_store_record(v, L.e, g, L, outcome, j);
+    L.e += v.lanes;
+    return true;
+}
+
 template <typename MaskT>
 __global__ void __launch_bounds__(256, 1) k_eval_episodes(StepArgs a, EvalArgs v)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = (int)threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int tid = (int)threadIdx.x;
+    const EvalRun &run = v.run;
     // ---- staging, once per workgroup: the image and the world by LDS-DMA, fc2 / b2 through registers
-    float *img = reinterpret_cast<float *>(smem + v.img_off);
-    float *W2 = reinterpret_cast<float *>(smem + v.w2_off);        // [16][64]
+    float *img = reinterpret_cast<float *>(smem + run.img_off);
+    float *W2 = reinterpret_cast<float *>(smem + run.w2_off);      // [16][64]
     float *b2 = W2 + uavq::kMaxOut * uavq::kHid;                    // [16]
     uavq::img_glds(img, v.img, wv);
     if (wv >= 2) stage_copy_glds(smem, a, wv - 2, 2);               // (as k_step_coop: the world through wavefronts 2-3)
-    {
-        const uavq::NetDev nl = uavq::net_view(v.local, v.n2);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (tid + 256 * k < v.n2 * uavq::kHid) W2[tid + 256 * k] = nl.W2[tid + 256 * k];
-        if (tid < v.n2) b2[tid] = nl.b2[tid];
-    }
+    eval_stage_w2(W2, b2, uavq::net_view(v.local, v.n2), v.n2, tid);
     Agent g = {};
     EvalLane L = {};
     L.e = (int)blockIdx.x * 256 + tid;                               // this lane's first episode (installed at the loop's top)
@@ -1741,99 +1866,33 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes(StepArgs a, EvalArgs v
     __syncthreads();                                                 // world, image, fc2 staged
     const WorldLds<MaskT> w = world_view<MaskT>(smem, a);
     const uavq::W1Split W1 = uavq::w1split_at(img);
-    unsigned char *slot = smem + v.slot_off + wv * v.slot_bytes;
+    unsigned char *slot = smem + run.slot_off + wv * run.slot_bytes;
     ObsWaveLds *Q = reinterpret_cast<ObsWaveLds *>(slot);           // the observation work queue, then (same bytes) the rows
     uint32_t *rows = reinterpret_cast<uint32_t *>(slot);
-    const int r16 = lane & 15, grp = lane >> 4;
     const int A = a.n_actions;
     for (;;) {
-        if (install) eval_install(a, v, g, L);                       // (one call site: the installation is inlined once)
+        if (install) eval_install(a, run, g, L);                     // (one call site: the installation is inlined once)
         install = false;
-        if (__ballot(L.e < v.n) == 0ull) break;
-        const bool have = L.e < v.n;
-        // ---- 1. state_PathPlan of the current state, as a packed row (store_obs_row_packed's layout) in registers
-        const ObsBits bits = obs_bits_queued(w, Q, g.o.px, g.o.py, g.o.pz, have);
-        const ObsScalars sc = obs_scalars(g.o, g.head);
-        uavq::PRow R;
-        ctile_mask_words(bits, R.m0, R.m1, R.m2);
-#pragma unroll
-        for (int k = 0; k < 11; ++k) R.sc[k] = sc.f[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) R.sg[k] = sc.f[11 + k];
-        if (!have) {                                                 // idle lane: a zero row, result discarded
-            R.m0 = R.m1 = R.m2 = 0u;
-#pragma unroll
-            for (int k = 0; k < 11; ++k) R.sc[k] = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) R.sg[k] = 0.0f;
-        }
-        wave_lds_sync();                                             // (the queue's last reads are done: the rows take its bytes)
-        uavq::prow_store_lds(rows + lane * kPackedDwords, R);
-        wave_lds_sync();
-        // ---- 2. Q(s) of the 64 rows: four 16-row strips, lane 16 st + r keeps strip st
-        float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 1
-        for (int st = 0; st < 4; ++st) {
-            uavq::PRow Rs;
-            uavq::prow_load(Rs, rows + (16 * st + r16) * kPackedDwords);
-            uavq::floatx4 h[4];
-            uavq::fwd_strip_split<false>(W1, Rs, h);
-            uavq::W2Frag<4> F;
-            uavq::w2_load<4>(F, W2, b2, v.n2);
-            float qs[4];
-            uavq::q_strip<4>(h, F, v.n2, A, v.dueling, qs);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) q[k] = grp == st ? qs[k] : q[k];
-        }
-        wave_lds_sync();                                             // the rows are read: the next iteration's queue may take the bytes
+        if (__ballot(L.e < run.n) == 0ull) break;
+        const bool have = L.e < run.n;
+        const uavq::PRow R = eval_obs_row(w, Q, g, have);
+        float q[4];
+        eval_forward_f32(W1, W2, b2, rows, R, lane, v.n2, A, v.dueling, q);
         if (have) {
-            // ---- the action: k_dqn_act_packed's greedy branch (first maximum, strict >); eps > 0: a uniform action on a draw < eps
-            int act = 0;
-            float bq = q[0];
-#pragma unroll
-            for (int k = 1; k < 4; ++k)
-                if (k < A && q[k] > bq) { bq = q[k]; act = k; }
-            if (v.eps > 0.0f) {
-                const uint4 rn = philox4x32_10(make_uint4((uint32_t)L.e, (uint32_t)L.steps, 0u, 0xe75fu),
-                                               make_uint2((uint32_t)v.seed, (uint32_t)(v.seed >> 32)));
-                const float u = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
-                if (u < v.eps) act = (int)(((uint64_t)rn.y * (uint64_t)A) >> 32);
-            }
-            // ---- 3. update_PathPlan (UAV.py:397-513): step_agent's pieces
+            const int act = eval_dqn_action(q, A, v.eps, run.seed, L.e, L.steps);
             const int j = L.e % a.U;
             const double a0 = decode_action(RawAction{(uint32_t)act, 0u}, UAVENV_ACT_INDEX_I32, A);
-            PreStep P;
-            step_pre(a, a0, g, P);
-            if (P.moved) g.head = angle_of<true>(g.o.vx, g.o.vy);   // :423
-            double r = 0.0;
-            int ret_done = 0, info = UAVENV_INFO_NORMAL;
-            bool head_set = false;
-            step_post<MaskT, false, true>(a, w, L.e, a0, g, P, r, ret_done, info, head_set);
-            g.o.n_rem = g.n_total - g.sub_idx;
-            L.steps += 1;
-            L.ret += r;
-            L.energy += fly_power(a.pw, g.o.V, j);
-            // a move always changes x or y (|V_vector| = Max_V > 0): the position is back where it was only after :425-428
-            if (P.moved && g.o.px == P.ox && g.o.py == P.oy && g.o.pz == P.oz) L.collisions += 1;
-            if (L.steps <= v.traj_steps) {
-                double *p = v.traj_pos + ((size_t)L.e * (v.traj_steps + 1) + L.steps) * 3;
-                p[0] = g.o.px; p[1] = g.o.py; p[2] = g.o.pz;
-                v.traj_act[(size_t)L.e * v.traj_steps + L.steps - 1] = (int8_t)act;
-            }
-            // ---- 4. the end of the episode: record, then the next episode of this lane
-            const bool trunc = (v.max_steps > 0 && L.steps >= v.max_steps) || L.steps >= L.cap;
-            if (g.done || trunc) {
-                const int outcome = g.done ? (info == UAVENV_INFO_LOSE ? UAVENV_EVAL_LOSE : UAVENV_EVAL_SUCCESS) : UAVENV_EVAL_TRUNCATED;
-                eval_store_record(v, L.e, g, L, outcome, j);
-                L.e += v.lanes;
-                install = true;
-            }
+            int info;
+            if (eval_step<MaskT, false>(a, w, run, a0, j, g, L, info))
+                v.traj_act[(size_t)L.e * run.traj_steps + L.steps - 1] = (int8_t)act;
+            install = eval_episode_end(run, g, L, info, j);
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// Greedy evaluation of an f16-MFMA net (uavenv_eval_episodes_f16; BASELINE configs[2]): k_eval_episodes' loop, line for line, with
+// Greedy evaluation of an f16-MFMA net (uavenv_eval_episodes_f16; BASELINE configs[2]): k_eval_episodes' loop -- the same shared
+// pieces: eval_obs_row, eval_stage_w2, eval_dqn_action, eval_step, eval_episode_end -- around a strip loop of its own, with
 // the f16-MFMA forward of k_dqn_act_h as the policy -- what an f16 learner acts with, not its f32 master weights under the f32
 // forward.  fc1 + b1 are staged once per workgroup as the f16 tile of polh_wave ([64][kPolLdW], through registers: v.img is not
 // used, v.img_off is the tile's offset); fc2 / b2 stay f32.  The lane's row goes into a wave-private 16-row strip as 104 halves
@@ -1847,18 +1906,16 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_h(StepArgs a, EvalArgs
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = (int)threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int tid = (int)threadIdx.x;
+    const EvalRun &run = v.run;
     // ---- staging, once per workgroup: the world by LDS-DMA, fc1 + b1 (to f16) and fc2 / b2 through registers
-    _Float16 *Wt = reinterpret_cast<_Float16 *>(smem + v.img_off);  // [64][kPolLdW]
-    float *W2 = reinterpret_cast<float *>(smem + v.w2_off);        // [16][64]
+    _Float16 *Wt = reinterpret_cast<_Float16 *>(smem + run.img_off);   // [64][kPolLdW]
+    float *W2 = reinterpret_cast<float *>(smem + run.w2_off);      // [16][64]
     float *b2 = W2 + uavq::kMaxOut * uavq::kHid;                    // [16]
     if (wv >= 2) stage_copy_glds(smem, a, wv - 2, 2);               // (as k_eval_episodes: the world through wavefronts 2-3)
     {
         const uavq::NetDev nl = uavq::net_view(v.local, v.n2);
         uavq::polh_stage_tile(Wt, nl);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (tid + 256 * k < v.n2 * uavq::kHid) W2[tid + 256 * k] = nl.W2[tid + 256 * k];
-        if (tid < v.n2) b2[tid] = nl.b2[tid];
+        eval_stage_w2(W2, b2, nl, v.n2, tid);
     }
     Agent g = {};
     EvalLane L = {};
@@ -1866,34 +1923,19 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_h(StepArgs a, EvalArgs
     bool install = true;
     __syncthreads();                                                 // world, fc1 tile, fc2 staged
     const WorldLds<MaskT> w = world_view<MaskT>(smem, a);
-    unsigned char *slot = smem + v.slot_off + wv * v.slot_bytes;
+    unsigned char *slot = smem + run.slot_off + wv * run.slot_bytes;
     ObsWaveLds *Q = reinterpret_cast<ObsWaveLds *>(slot);           // the observation work queue, then (same bytes) the strip
     _Float16 *strip = reinterpret_cast<_Float16 *>(slot);           // [16][kPolLdW]
     const int r16 = lane & 15, grp = lane >> 4;
     const int A = a.n_actions;
     for (;;) {
-        if (install) eval_install(a, v, g, L);                       // (one call site: the installation is inlined once)
+        if (install) eval_install(a, run, g, L);                     // (one call site: the installation is inlined once)
         install = false;
-        if (__ballot(L.e < v.n) == 0ull) break;
-        const bool have = L.e < v.n;
-        // ---- 1. state_PathPlan of the current state, as a packed row (store_obs_row_packed's layout) in registers
-        const ObsBits bits = obs_bits_queued(w, Q, g.o.px, g.o.py, g.o.pz, have);
-        const ObsScalars sc = obs_scalars(g.o, g.head);
-        uavq::PRow R;
-        ctile_mask_words(bits, R.m0, R.m1, R.m2);
-#pragma unroll
-        for (int k = 0; k < 11; ++k) R.sc[k] = sc.f[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) R.sg[k] = sc.f[11 + k];
-        if (!have) {                                                 // idle lane: a zero row, result discarded
-            R.m0 = R.m1 = R.m2 = 0u;
-#pragma unroll
-            for (int k = 0; k < 11; ++k) R.sc[k] = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) R.sg[k] = 0.0f;
-        }
+        if (__ballot(L.e < run.n) == 0ull) break;
+        const bool have = L.e < run.n;
+        const uavq::PRow R = eval_obs_row(w, Q, g, have);
         wave_lds_sync();                                             // (the queue's last reads are done: the strip takes its bytes)
-        // ---- 2. Q(s) of the 64 rows: four 16-row strips, lane 16 st + r writes row r of strip st and keeps its result
+        // ---- Q(s) of the 64 rows: four 16-row strips, lane 16 st + r writes row r of strip st and keeps its result
         float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 1
         for (int st = 0; st < 4; ++st) {
@@ -1910,47 +1952,13 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_h(StepArgs a, EvalArgs
             wave_lds_sync();                                         // the strip is read: the next strip (or the next queue) may take the bytes
         }
         if (have) {
-            // ---- the action: k_dqn_act_h's greedy branch (first maximum, strict >); eps > 0: a uniform action on a draw < eps
-            int act = 0;
-            float bq = q[0];
-#pragma unroll
-            for (int k = 1; k < 4; ++k)
-                if (k < A && q[k] > bq) { bq = q[k]; act = k; }
-            if (v.eps > 0.0f) {
-                const uint4 rn = philox4x32_10(make_uint4((uint32_t)L.e, (uint32_t)L.steps, 0u, 0xe75fu),
-                                               make_uint2((uint32_t)v.seed, (uint32_t)(v.seed >> 32)));
-                const float u = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
-                if (u < v.eps) act = (int)(((uint64_t)rn.y * (uint64_t)A) >> 32);
-            }
-            // ---- 3. update_PathPlan (UAV.py:397-513): step_agent's pieces
+            const int act = eval_dqn_action(q, A, v.eps, run.seed, L.e, L.steps);
             const int j = L.e % a.U;
             const double a0 = decode_action(RawAction{(uint32_t)act, 0u}, UAVENV_ACT_INDEX_I32, A);
-            PreStep P;
-            step_pre(a, a0, g, P);
-            if (P.moved) g.head = angle_of<true>(g.o.vx, g.o.vy);   // :423
-            double r = 0.0;
-            int ret_done = 0, info = UAVENV_INFO_NORMAL;
-            bool head_set = false;
-            step_post<MaskT, false, true>(a, w, L.e, a0, g, P, r, ret_done, info, head_set);
-            g.o.n_rem = g.n_total - g.sub_idx;
-            L.steps += 1;
-            L.ret += r;
-            L.energy += fly_power(a.pw, g.o.V, j);
-            // a move always changes x or y (|V_vector| = Max_V > 0): the position is back where it was only after :425-428
-            if (P.moved && g.o.px == P.ox && g.o.py == P.oy && g.o.pz == P.oz) L.collisions += 1;
-            if (L.steps <= v.traj_steps) {
-                double *p = v.traj_pos + ((size_t)L.e * (v.traj_steps + 1) + L.steps) * 3;
-                p[0] = g.o.px; p[1] = g.o.py; p[2] = g.o.pz;
-                v.traj_act[(size_t)L.e * v.traj_steps + L.steps - 1] = (int8_t)act;
-            }
-            // ---- 4. the end of the episode: record, then the next episode of this lane
-            const bool trunc = (v.max_steps > 0 && L.steps >= v.max_steps) || L.steps >= L.cap;
-            if (g.done || trunc) {
-                const int outcome = g.done ? (info == UAVENV_INFO_LOSE ? UAVENV_EVAL_LOSE : UAVENV_EVAL_SUCCESS) : UAVENV_EVAL_TRUNCATED;
-                eval_store_record(v, L.e, g, L, outcome, j);
-                L.e += v.lanes;
-                install = true;
-            }
+            int info;
+            if (eval_step<MaskT, false>(a, w, run, a0, j, g, L, info))
+                v.traj_act[(size_t)L.e * run.traj_steps + L.steps - 1] = (int8_t)act;
+            install = eval_episode_end(run, g, L, info, j);
         }
     }
 }
@@ -1961,25 +1969,21 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_h(StepArgs a, EvalArgs
 // blockIdx.y = actor: the workgroups of slice y stage actor y once (stage_actor_split: fc1 + b1 into the split form; fc_mu / fc_std
 // and their biases as a [4][64] + [4] block, all through registers; the world by LDS-DMA) and fly the episodes e = y (mod n_actors),
 // lane l of the slice starting with episode y + n_actors l; a lane's next episode is e + (lanes of the whole grid).
-// The forward is k_sac_act's (csrc/sac.hip): fwd_strip_split + w2_load<4> / q_strip<4>(.., 4, 4, 0, .) per 16-row strip -- the same
-// operands in the same K positions, the same MFMA order -- then actor_head_one on the lane's own row: component 0 always, component 1
-// only where the trajectory wants it.  Nothing of the forward is live across the step but the lane's four head outputs.
-// APF: update_PathPlan is step_pre / step_post<MaskT, true, true> (Adjust_subgoal by the lane itself, adjust_subgoals_lane, whose lists
+// The forward is k_sac_act's (csrc/sac.hip): eval_forward_f32 with (n2, n_actions, dueling) = (4, 4, 0), i.e. fwd_strip_split +
+// w2_load<4> / q_strip<4>(.., 4, 4, 0, .) per 16-row strip -- the same operands in the same K positions, the same MFMA order --
+// then actor_head_one on the lane's own row: component 0 always, component 1 only where the trajectory wants it.  Nothing of the
+// forward is live across the step but the lane's four head outputs.  The row, the step and the episode's end are the shared pieces.
+// APF: update_PathPlan (eval_step<MaskT, true>) is step_pre / step_post<MaskT, true, true> (Adjust_subgoal by the lane itself, adjust_subgoals_lane, whose lists
 // are bit-identical to k_apf_adjust's) on the lane's OWN [K][3] list: a.st.sub is the evaluation workspace here, not the env's lists,
 // and every index handed to apply_reset / step_post is the resident lane `li` -- they use it for list addressing only; what depends on
 // the UAV slot (power parameters, the record's slot) takes e mod U.  Non-APF episodes read the scenario row in place (g.scn >= 0).
 // ------------------------------------------------------------------------------------------------
 struct SacEvalArgs {
+    EvalRun run;                       // (LDS: fc1 in the split form, fc_mu / fc_std (+ biases), per-wave slots)
     const float *actor[UAVENV_SAC_LOOP_MAX_SLOTS];   // flat parameter blocks (fc1.w | fc1.b | fc_mu.w | fc_std.w | fc_mu.b | fc_std.b)
-    const double *v0;                  // nullable [n][2]
-    uint4 *rec;                        // [n] x 64 bytes (UavEvalRecord)
-    double *traj_pos;                  // nullable [n][traj_steps + 1][3]
     float *traj_act;                   // nullable [n][traj_steps][2]
-    uint64_t seed;
     float bound;
     int32_t mode, n_actors;
-    int32_t n, first, max_steps, traj_steps, lanes;  // lanes: of the whole grid = a lane's episode stride
-    int32_t img_off, w2_off, slot_off, slot_bytes;   // LDS byte offsets: fc1 split, fc_mu / fc_std (+ biases), per-wave slots
 };
 
 // The noise of UAVENV_EVAL_SAC_SAMPLE for (episode, step): both components.  ONE function for the episode kernel and for
@@ -2013,11 +2017,12 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_sac(StepArgs a, SacEva
     const int lane = (int)threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int tid = (int)threadIdx.x;
     const int y = (int)blockIdx.y;
+    const EvalRun &run = v.run;
     const float *actor = v.actor[y];
     // ---- staging, once per workgroup: the world by LDS-DMA, the actor through registers
-    float *W2 = reinterpret_cast<float *>(smem + v.w2_off);        // fc_mu | fc_std: [4][64]
+    float *W2 = reinterpret_cast<float *>(smem + run.w2_off);      // fc_mu | fc_std: [4][64]
     float *b2 = W2 + 4 * uavq::kHid;                                // [4]
-    const uavq::W1Split W1 = uavq::w1split_at(reinterpret_cast<float *>(smem + v.img_off));
+    const uavq::W1Split W1 = uavq::w1split_at(reinterpret_cast<float *>(smem + run.img_off));
     if (wv >= 2) stage_copy_glds(smem, a, wv - 2, 2);               // (as k_eval_episodes: the world through wavefronts 2-3)
     {
         const uavq::NetDev nl = uavq::net_view(actor, 4);
@@ -2034,85 +2039,30 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_sac(StepArgs a, SacEva
     bool install = true;
     __syncthreads();                                                 // world and actor staged
     const WorldLds<MaskT> w = world_view<MaskT>(smem, a);
-    unsigned char *slot = smem + v.slot_off + wv * v.slot_bytes;
+    unsigned char *slot = smem + run.slot_off + wv * run.slot_bytes;
     ObsWaveLds *Q = reinterpret_cast<ObsWaveLds *>(slot);           // the observation work queue, then (same bytes) the rows
     uint32_t *rows = reinterpret_cast<uint32_t *>(slot);
-    const int r16 = lane & 15, grp = lane >> 4;
     for (;;) {
-        if (install) eval_install<APF>(a, v, g, L, li);              // (one call site: the installation is inlined once)
+        if (install) eval_install<APF>(a, run, g, L, li);            // (one call site: the installation is inlined once)
         install = false;
-        if (__ballot(L.e < v.n) == 0ull) break;
-        const bool have = L.e < v.n;
-        // ---- 1. state_PathPlan of the current state, as a packed row in registers (as k_eval_episodes)
-        const ObsBits bits = obs_bits_queued(w, Q, g.o.px, g.o.py, g.o.pz, have);
-        const ObsScalars sc = obs_scalars(g.o, g.head);
-        uavq::PRow R;
-        ctile_mask_words(bits, R.m0, R.m1, R.m2);
-#pragma unroll
-        for (int k = 0; k < 11; ++k) R.sc[k] = sc.f[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) R.sg[k] = sc.f[11 + k];
-        if (!have) {                                                 // idle lane: a zero row, result discarded
-            R.m0 = R.m1 = R.m2 = 0u;
-#pragma unroll
-            for (int k = 0; k < 11; ++k) R.sc[k] = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) R.sg[k] = 0.0f;
-        }
-        wave_lds_sync();                                             // (the queue's last reads are done: the rows take its bytes)
-        uavq::prow_store_lds(rows + lane * kPackedDwords, R);
-        wave_lds_sync();
-        // ---- 2. fc_mu | fc_std of the 64 rows: four 16-row strips, lane 16 st + r keeps strip st
-        float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 1
-        for (int st = 0; st < 4; ++st) {
-            uavq::PRow Rs;
-            uavq::prow_load(Rs, rows + (16 * st + r16) * kPackedDwords);
-            uavq::floatx4 h[4];
-            uavq::fwd_strip_split<false>(W1, Rs, h);
-            uavq::W2Frag<4> F;
-            uavq::w2_load<4>(F, W2, b2, 4);
-            float os[4];
-            uavq::q_strip<4>(h, F, 4, 4, 0, os);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = grp == st ? os[k] : o[k];
-        }
-        wave_lds_sync();                                             // the rows are read: the next iteration's queue may take the bytes
+        if (__ballot(L.e < run.n) == 0ull) break;
+        const bool have = L.e < run.n;
+        const uavq::PRow R = eval_obs_row(w, Q, g, have);
+        float o[4];                                                  // fc_mu | fc_std of the lane's row
+        eval_forward_f32(W1, W2, b2, rows, R, lane, 4, 4, 0, o);
         if (have) {
             // ---- the action: get_action (SAC_Trainer.py:444-448), component 0 steers (UAV.py:414)
             float2 z = make_float2(0.0f, 0.0f);
-            if (v.mode == UAVENV_EVAL_SAC_SAMPLE) z = eval_sac_noise(v.seed, L.e, L.steps);
+            if (v.mode == UAVENV_EVAL_SAC_SAMPLE) z = eval_sac_noise(run.seed, L.e, L.steps);
             const float act0 = uavq::actor_head_one(o[0], o[2], z.x).act * v.bound;
-            // ---- 3. update_PathPlan (UAV.py:397-513): step_agent's pieces
             const int j = L.e % a.U;
             const double a0 = decode_action(RawAction{__float_as_uint(act0), 0u}, UAVENV_ACT_STEER_F32, a.n_actions);
-            PreStep P;
-            step_pre(a, a0, g, P);
-            if (P.moved) g.head = angle_of<true>(g.o.vx, g.o.vy);   // :423
-            double r = 0.0;
-            int ret_done = 0, info = UAVENV_INFO_NORMAL;
-            bool head_set = false;
-            step_post<MaskT, APF, true>(a, w, APF ? li : L.e, a0, g, P, r, ret_done, info, head_set);
-            g.o.n_rem = g.n_total - g.sub_idx;
-            L.steps += 1;
-            L.ret += r;
-            L.energy += fly_power(a.pw, g.o.V, j);
-            // a move always changes x or y (|V_vector| = Max_V > 0): the position is back where it was only after :425-428
-            if (P.moved && g.o.px == P.ox && g.o.py == P.oy && g.o.pz == P.oz) L.collisions += 1;
-            if (L.steps <= v.traj_steps) {
-                double *p = v.traj_pos + ((size_t)L.e * (v.traj_steps + 1) + L.steps) * 3;
-                p[0] = g.o.px; p[1] = g.o.py; p[2] = g.o.pz;
-                const float act1 = uavq::actor_head_one(o[1], o[3], z.y).act * v.bound;
-                reinterpret_cast<float2 *>(v.traj_act)[(size_t)L.e * v.traj_steps + L.steps - 1] = make_float2(act0, act1);
+            int info;
+            if (eval_step<MaskT, APF>(a, w, run, a0, j, g, L, info, li)) {
+                const float act1 = uavq::actor_head_one(o[1], o[3], z.y).act * v.bound;   // (only the trajectory wants it)
+                reinterpret_cast<float2 *>(v.traj_act)[(size_t)L.e * run.traj_steps + L.steps - 1] = make_float2(act0, act1);
             }
-            // ---- 4. the end of the episode: record, then the next episode of this lane
-            const bool trunc = (v.max_steps > 0 && L.steps >= v.max_steps) || L.steps >= L.cap;
-            if (g.done || trunc) {
-                const int outcome = g.done ? (info == UAVENV_INFO_LOSE ? UAVENV_EVAL_LOSE : UAVENV_EVAL_SUCCESS) : UAVENV_EVAL_TRUNCATED;
-                eval_store_record(v, L.e, g, L, outcome, j);
-                L.e += v.lanes;
-                install = true;
-            }
+            install = eval_episode_end(run, g, L, info, j);
         }
     }
 }
@@ -2122,24 +2072,19 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_sac(StepArgs a, SacEva
 // and the APF step of k_eval_episodes_sac.  blockIdx.y = net: the workgroups of slice y stage net y once (its layer-1 image by
 // LDS-DMA from image y of v.img, fc2 / b2 through registers from v.local[y]; the world by LDS-DMA) and fly the episodes
 // e = y (mod n_nets), lane l of the slice starting with episode y + n_nets l; a lane's next episode is e + (lanes of the whole grid).
-// The forward, the first-maximum action, the eps draw and the heading are k_eval_episodes' (same operands in the same K positions,
-// same MFMA order: the same Q values).  APF: update_PathPlan is step_pre / step_post<MaskT, true, true> on the lane's OWN [K][3] list
+// The forward, the first-maximum action, the eps draw and the heading are k_eval_episodes' (eval_forward_f32, eval_dqn_action,
+// eval_step: the same Q values).  APF: update_PathPlan (eval_step<MaskT, true>) is step_pre / step_post<MaskT, true, true> on the lane's OWN [K][3] list
 // (a.st.sub is the evaluation workspace, every index handed to apply_reset / step_post is the resident lane `li`); what depends on
 // the UAV slot (power parameters, the record's slot) takes e mod U.  Non-APF episodes read the scenario row in place.
 // ------------------------------------------------------------------------------------------------
 struct SlotsEvalArgs {
+    EvalRun run;
     const float *local[UAVENV_SAC_LOOP_MAX_SLOTS];   // the nets' q_local flat blocks (fc2 / b2 are read from them)
     const float *img;                  // n_nets layer-1 images in the split form, image y at img + y * kSplitF
-    const double *v0;                  // nullable [n][2]
-    uint4 *rec;                        // [n] x 64 bytes (UavEvalRecord)
-    double *traj_pos;                  // nullable [n][traj_steps + 1][3]
     int8_t *traj_act;                  // nullable [n][traj_steps]
-    uint64_t seed;
     float eps;
     int32_t n_nets;
-    int32_t n, first, max_steps, traj_steps, lanes;  // lanes: of the whole grid = a lane's episode stride
     int32_t n2, dueling;
-    int32_t img_off, w2_off, slot_off, slot_bytes;   // LDS byte offsets: image, fc2 (+ b2), per-wave slots
 };
 
 template <typename MaskT, bool APF>
@@ -2149,19 +2094,14 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_slots(StepArgs a, Slot
     const int lane = (int)threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int tid = (int)threadIdx.x;
     const int y = (int)blockIdx.y;
+    const EvalRun &run = v.run;
     // ---- staging, once per workgroup: net y's image and the world by LDS-DMA, its fc2 / b2 through registers
-    float *img = reinterpret_cast<float *>(smem + v.img_off);
-    float *W2 = reinterpret_cast<float *>(smem + v.w2_off);        // [16][64]
+    float *img = reinterpret_cast<float *>(smem + run.img_off);
+    float *W2 = reinterpret_cast<float *>(smem + run.w2_off);      // [16][64]
     float *b2 = W2 + uavq::kMaxOut * uavq::kHid;                    // [16]
     uavq::img_glds(img, v.img + (size_t)y * uavq::kSplitF, wv);
     if (wv >= 2) stage_copy_glds(smem, a, wv - 2, 2);               // (as k_eval_episodes: the world through wavefronts 2-3)
-    {
-        const uavq::NetDev nl = uavq::net_view(v.local[y], v.n2);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (tid + 256 * k < v.n2 * uavq::kHid) W2[tid + 256 * k] = nl.W2[tid + 256 * k];
-        if (tid < v.n2) b2[tid] = nl.b2[tid];
-    }
+    eval_stage_w2(W2, b2, uavq::net_view(v.local[y], v.n2), v.n2, tid);
     Agent g = {};
     EvalLane L = {};
     const int li = ((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * 256 + tid;   // resident lane: its sub-goal list (APF)
@@ -2170,93 +2110,26 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_slots(StepArgs a, Slot
     __syncthreads();                                                 // world, image, fc2 staged
     const WorldLds<MaskT> w = world_view<MaskT>(smem, a);
     const uavq::W1Split W1 = uavq::w1split_at(img);
-    unsigned char *slot = smem + v.slot_off + wv * v.slot_bytes;
+    unsigned char *slot = smem + run.slot_off + wv * run.slot_bytes;
     ObsWaveLds *Q = reinterpret_cast<ObsWaveLds *>(slot);           // the observation work queue, then (same bytes) the rows
     uint32_t *rows = reinterpret_cast<uint32_t *>(slot);
-    const int r16 = lane & 15, grp = lane >> 4;
     const int A = a.n_actions;
     for (;;) {
-        if (install) eval_install<APF>(a, v, g, L, li);              // (one call site: the installation is inlined once)
+        if (install) eval_install<APF>(a, run, g, L, li);            // (one call site: the installation is inlined once)
         install = false;
-        if (__ballot(L.e < v.n) == 0ull) break;
-        const bool have = L.e < v.n;
-        // ---- 1. state_PathPlan of the current state, as a packed row in registers (as k_eval_episodes)
-        const ObsBits bits = obs_bits_queued(w, Q, g.o.px, g.o.py, g.o.pz, have);
-        const ObsScalars sc = obs_scalars(g.o, g.head);
-        uavq::PRow R;
-        ctile_mask_words(bits, R.m0, R.m1, R.m2);
-#pragma unroll
-        for (int k = 0; k < 11; ++k) R.sc[k] = sc.f[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) R.sg[k] = sc.f[11 + k];
-        if (!have) {                                                 // idle lane: a zero row, result discarded
-            R.m0 = R.m1 = R.m2 = 0u;
-#pragma unroll
-            for (int k = 0; k < 11; ++k) R.sc[k] = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) R.sg[k] = 0.0f;
-        }
-        wave_lds_sync();                                             // (the queue's last reads are done: the rows take its bytes)
-        uavq::prow_store_lds(rows + lane * kPackedDwords, R);
-        wave_lds_sync();
-        // ---- 2. Q(s) of the 64 rows: four 16-row strips, lane 16 st + r keeps strip st (as k_eval_episodes)
-        float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 1
-        for (int st = 0; st < 4; ++st) {
-            uavq::PRow Rs;
-            uavq::prow_load(Rs, rows + (16 * st + r16) * kPackedDwords);
-            uavq::floatx4 h[4];
-            uavq::fwd_strip_split<false>(W1, Rs, h);
-            uavq::W2Frag<4> F;
-            uavq::w2_load<4>(F, W2, b2, v.n2);
-            float qs[4];
-            uavq::q_strip<4>(h, F, v.n2, A, v.dueling, qs);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) q[k] = grp == st ? qs[k] : q[k];
-        }
-        wave_lds_sync();                                             // the rows are read: the next iteration's queue may take the bytes
+        if (__ballot(L.e < run.n) == 0ull) break;
+        const bool have = L.e < run.n;
+        const uavq::PRow R = eval_obs_row(w, Q, g, have);
+        float q[4];
+        eval_forward_f32(W1, W2, b2, rows, R, lane, v.n2, A, v.dueling, q);
         if (have) {
-            // ---- the action: k_eval_episodes' (first maximum, strict >; eps > 0: a uniform action on a draw < eps)
-            int act = 0;
-            float bq = q[0];
-#pragma unroll
-            for (int k = 1; k < 4; ++k)
-                if (k < A && q[k] > bq) { bq = q[k]; act = k; }
-            if (v.eps > 0.0f) {
-                const uint4 rn = philox4x32_10(make_uint4((uint32_t)L.e, (uint32_t)L.steps, 0u, 0xe75fu),
-                                               make_uint2((uint32_t)v.seed, (uint32_t)(v.seed >> 32)));
-                const float u = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
-                if (u < v.eps) act = (int)(((uint64_t)rn.y * (uint64_t)A) >> 32);
-            }
-            // ---- 3. update_PathPlan (UAV.py:397-513): step_agent's pieces
+            const int act = eval_dqn_action(q, A, v.eps, run.seed, L.e, L.steps);
             const int j = L.e % a.U;
             const double a0 = decode_action(RawAction{(uint32_t)act, 0u}, UAVENV_ACT_INDEX_I32, A);
-            PreStep P;
-            step_pre(a, a0, g, P);
-            if (P.moved) g.head = angle_of<true>(g.o.vx, g.o.vy);   // :423
-            double r = 0.0;
-            int ret_done = 0, info = UAVENV_INFO_NORMAL;
-            bool head_set = false;
-            step_post<MaskT, APF, true>(a, w, APF ? li : L.e, a0, g, P, r, ret_done, info, head_set);
-            g.o.n_rem = g.n_total - g.sub_idx;
-            L.steps += 1;
-            L.ret += r;
-            L.energy += fly_power(a.pw, g.o.V, j);
-            // a move always changes x or y (|V_vector| = Max_V > 0): the position is back where it was only after :425-428
-            if (P.moved && g.o.px == P.ox && g.o.py == P.oy && g.o.pz == P.oz) L.collisions += 1;
-            if (L.steps <= v.traj_steps) {
-                double *p = v.traj_pos + ((size_t)L.e * (v.traj_steps + 1) + L.steps) * 3;
-                p[0] = g.o.px; p[1] = g.o.py; p[2] = g.o.pz;
-                v.traj_act[(size_t)L.e * v.traj_steps + L.steps - 1] = (int8_t)act;
-            }
-            // ---- 4. the end of the episode: record, then the next episode of this lane
-            const bool trunc = (v.max_steps > 0 && L.steps >= v.max_steps) || L.steps >= L.cap;
-            if (g.done || trunc) {
-                const int outcome = g.done ? (info == UAVENV_INFO_LOSE ? UAVENV_EVAL_LOSE : UAVENV_EVAL_SUCCESS) : UAVENV_EVAL_TRUNCATED;
-                eval_store_record(v, L.e, g, L, outcome, j);
-                L.e += v.lanes;
-                install = true;
-            }
+            int info;
+            if (eval_step<MaskT, APF>(a, w, run, a0, j, g, L, info, li))
+                v.traj_act[(size_t)L.e * run.traj_steps + L.steps - 1] = (int8_t)act;
+            install = eval_episode_end(run, g, L, info, j);
         }
     }
 }
@@ -3180,199 +3053,231 @@ int uavenv_threaten_rate_allpairs(UavEnv *e, const double *xyz, uint8_t *out, in
     return threaten_impl(e, xyz, out, n, stream, true);
 }
 
+}  // extern "C"
+
+// ---- the four evaluation entries' shared host side.  `name` is the entry's, for the messages.  Every entry is ordered alike: all
+// refusals (the range check of eval_grid included), then allocations, then the image launches, then the kernel -- a refused call
+// has allocated and enqueued nothing.  U: UavEvalArgs or UavSacEvalArgs (the fields used here have the same names in both).
+
+// what every entry refuses of the env and of the arguments.  local: the single net's block, whose alignment the single-net entries
+// report together with the records'; NULL where the entry checks its blocks itself
+template <typename U>
+static int eval_check_common(const char *name, const UavEnv *e, const U &u, const void *local)
+{
+    if (!e->have_world) return fail(UAVENV_EINVAL, "%s before uavenv_set_buildings", name);
+    if (u.n <= 0 || u.first < 0) return fail(UAVENV_EINVAL, "%s: n %d, first %d", name, u.n, u.first);
+    if (!u.records || ((((uintptr_t)u.records) | ((uintptr_t)local)) & 15u) != 0)
+        return local ? fail(UAVENV_EINVAL, "%s: records and net->local must be 16-byte aligned device pointers", name)
+                     : fail(UAVENV_EINVAL, "%s: records must be a 16-byte aligned device pointer", name);
+    const int given = (u.start_goal ? 1 : 0) + (u.sub ? 1 : 0) + (u.nsub ? 1 : 0);
+    if (given != 0 && given != 3) return fail(UAVENV_EINVAL, "%s: give all three scenario arrays or none", name);
+    if (given == 3 && u.m <= 0) return fail(UAVENV_EINVAL, "%s: m %d", name, u.m);
+    if (given == 0 && e->bank_m <= 0) return fail(UAVENV_EINVAL, "%s: no scenarios (the env has no bank)", name);
+    if (u.traj_steps < 0 || u.traj_steps >= (1 << 30) || (u.traj_steps > 0 && (!u.traj_pos || !u.traj_act)))
+        return fail(UAVENV_EINVAL, "%s: traj_steps %d needs both trajectory pointers", name, u.traj_steps);
+    if (u.max_steps < 0 || u.max_workgroups < 0) return fail(UAVENV_EINVAL, "%s: max_steps / max_workgroups < 0", name);
+    if ((((uintptr_t)u.start_goal) | ((uintptr_t)u.sub) | ((uintptr_t)u.v0) | ((uintptr_t)u.traj_pos)) & 7u)
+        return fail(UAVENV_EINVAL, "%s: misaligned f64 array", name);
+    const bool act2 = sizeof(*u.traj_act) > 1;                      // SAC: one float2 per step
+    if ((((uintptr_t)u.nsub) & 3u) || (act2 && (((uintptr_t)u.traj_act) & 7u)))
+        return fail(UAVENV_EINVAL, act2 ? "%s: misaligned nsub / traj_act" : "%s: misaligned nsub", name);
+    return UAVENV_OK;
+}
+
+// a DQN net the episode kernels take: the MFMA kind wanted, the uavenv_step_policy shape, at most 4 layer-2 outputs.  k >= 0: net k of several
+static int eval_check_dqn_net(const char *name, int k, const UavEnv *e, const UavDqnNet *net, int mfma_dtype)
+{
+    const int n2 = net->n_actions + (net->dueling ? 1 : 0);
+    if (net->local && net->mfma_dtype == mfma_dtype && net->w == uavq::kW && net->hid == uavq::kHid && net->n_actions >= 2 && n2 <= 4 &&
+        net->n_actions == e->cfg.n_actions)
+        return UAVENV_OK;
+    char who[96];
+    if (k >= 0) snprintf(who, sizeof(who), "%s: net %d", name, k);
+    else snprintf(who, sizeof(who), "%s", name);
+    return fail(UAVENV_EINVAL, "%s: needs an %s-MFMA net of w %d, hid %d, the env's %d actions, <= 4 outputs", who,
+                mfma_dtype == UAVENV_MFMA_F16 ? "f16" : "f32", uavq::kW, uavq::kHid, e->cfg.n_actions);
+}
+
+// the env's parameters and world; the scenario set in the bank's place; nothing the step launches own
+template <typename U>
+static StepArgs eval_step_args(const UavEnv *e, const U &u)
+{
+    StepArgs a = base_args(e);
+    a.moved_word = nullptr;
+    a.meta = nullptr;
+    a.meta_a1 = nullptr;
+    a.dbg = nullptr;
+    a.block = 256;
+    if (u.start_goal) {                // (all three or none: eval_check_common)
+        a.bank.start_goal = u.start_goal;
+        a.bank.sub = u.sub;
+        a.bank.nsub = u.nsub;
+        a.bank.m = u.m;
+    }
+    return a;
+}
+
+// the per-run fields from the caller's arguments, and the LDS carve-up behind the world blob: the layer-1 region (l1_bytes), the
+// layer-2 block (l2_floats), four wave slots (the observation work queue, then in the same bytes the kernel's rows: at least
+// slot_min bytes).  Returns the launch's dynamic LDS bytes.  (run.lanes: eval_grid)
+template <typename U>
+static size_t eval_run_setup(const UavEnv *e, const U &u, EvalRun &run, int l1_bytes, int l2_floats, int slot_min)
+{
+    run.v0 = u.v0;
+    run.rec = reinterpret_cast<uint4 *>(u.records);
+    run.traj_pos = u.traj_steps > 0 ? u.traj_pos : nullptr;
+    run.seed = u.seed;
+    run.n = u.n;
+    run.first = u.first;
+    run.max_steps = u.max_steps;
+    run.traj_steps = u.traj_steps;
+    run.img_off = (e->world_bytes + 15) & ~15;
+    run.w2_off = run.img_off + l1_bytes;
+    run.slot_off = (run.w2_off + l2_floats * 4 + 15) & ~15;
+    int slot = (int)sizeof(ObsWaveLds);
+    if (slot < slot_min) slot = slot_min;
+    run.slot_bytes = (slot + 15) & ~15;
+    return (size_t)run.slot_off + 4 * (size_t)run.slot_bytes;
+}
+
+// an episode kernel's instantiations by [mask width: 64, 32 bits][APF: off, on] (the single-net kernels have no APF form), and
+// the one for this env
+struct EvalKernels { const void *fn[2][2]; };
+static const void *eval_kernel(const UavEnv *e, const EvalKernels &k) { return k.fn[e->mask_bytes == 4 ? 1 : 0][e->cfg.apf_enabled == 1 ? 1 : 0]; }
+
+// grid.x for each of n_policies slices (grid.y): as many workgroups as stay resident beside the other slices', at most one per
+// 256 of a slice's episodes (or max_workgroups); run.lanes = the whole grid's.  Refuses an n whose last stride would overflow.
+static int eval_grid(const char *name, const UavEnv *e, const void *fn, size_t lds, int max_workgroups, int n_policies, EvalRun &run, int *grid_out)
+{
+    if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t per_policy = ((int64_t)run.n + n_policies - 1) / n_policies;
+    const int want = (int)((per_policy + 255) / 256);
+    int grid = want;
+    if (max_workgroups > 0) {
+        grid = max_workgroups < want ? max_workgroups : want;
+    } else {
+        int per_cu = 0, cus = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
+        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device));
+        const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1) / n_policies;
+        if (resident < grid) grid = (int)(resident > 0 ? resident : 1);
+    }
+    if (grid < 1) grid = 1;
+    const int64_t lanes = (int64_t)grid * n_policies * 256;
+    // (a lane's next episode is e + lanes in 32-bit arithmetic: the last one taken must still be representable)
+    if ((int64_t)run.n + lanes > (int64_t)INT32_MAX)
+        return fail(UAVENV_EINVAL, "%s: n %d + %lld lanes exceeds the episode index range", name, run.n, (long long)lanes);
+    run.lanes = (int32_t)lanes;
+    *grid_out = grid;
+    return UAVENV_OK;
+}
+
+// APF: one private [K][3] list per resident lane in the env-owned workspace, in the place of the env's own lists (e->st.sub), which
+// stay as they are.  (hipFree synchronises the device: an earlier evaluation still in flight has finished with the old workspace
+// before it goes.)
+static int eval_apf_workspace(UavEnv *e, StepArgs &a, int64_t lanes)
+{
+    if (e->eval_sub_lanes < lanes) {
+        (void)hipFree(e->eval_sub);
+        e->eval_sub = nullptr;
+        e->eval_sub_lanes = 0;
+        HIP_TRY(hipMalloc((void **)&e->eval_sub, (size_t)lanes * (size_t)a.K * 3 * sizeof(double)));
+        e->eval_sub_lanes = lanes;
+    }
+    a.st.sub = e->eval_sub;
+    return UAVENV_OK;
+}
+
+template <typename V>
+static int eval_launch(const void *fn, int grid, int n_policies, size_t lds, void *stream, StepArgs &a, V &v)
+{
+    void *params[2] = {&a, &v};
+    HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid, (unsigned)n_policies), dim3(256), params, lds, (hipStream_t)stream));
+    return UAVENV_OK;
+}
+
+#define EVAL_TRY(call)                                                                                                                 \
+    do {                                                                                                                               \
+        const int rc_ = (call);                                                                                                        \
+        if (rc_ != UAVENV_OK) return rc_;                                                                                              \
+    } while (0)
+
+extern "C" {
+
 int uavenv_eval_episodes(UavEnv *e, const UavDqnNet *net, const UavEvalArgs *args, void *stream)
 {
+    static const char *const name = "uavenv_eval_episodes";
+    static const EvalKernels kernels = {{{reinterpret_cast<const void *>(k_eval_episodes<uint64_t>), nullptr},
+                                         {reinterpret_cast<const void *>(k_eval_episodes<uint32_t>), nullptr}}};
     if (!e || !net || !args) return fail(UAVENV_EINVAL, "null argument");
     const UavEvalArgs &u = *args;
     if (e->cfg.apf_enabled == 1) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: APF envs are not supported");
-    if (!e->have_world) return fail(UAVENV_EINVAL, "uavenv_eval_episodes before uavenv_set_buildings");
-    const int n2 = net->n_actions + (net->dueling ? 1 : 0);
-    if (!net->local || net->mfma_dtype != UAVENV_MFMA_F32 || net->w != uavq::kW || net->hid != uavq::kHid || net->n_actions < 2 ||
-        n2 > 4 || net->n_actions != e->cfg.n_actions)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes: needs an f32-MFMA net of w %d, hid %d, the env's %d actions, <= 4 outputs",
-                    uavq::kW, uavq::kHid, e->cfg.n_actions);
-    if (u.n <= 0 || u.first < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: n %d, first %d", u.n, u.first);
-    if (!u.records || ((((uintptr_t)u.records) | ((uintptr_t)net->local)) & 15u) != 0)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes: records and net->local must be 16-byte aligned device pointers");
-    const int given = (u.start_goal ? 1 : 0) + (u.sub ? 1 : 0) + (u.nsub ? 1 : 0);
-    if (given != 0 && given != 3) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: give all three scenario arrays or none");
-    if (given == 3 && u.m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: m %d", u.m);
-    if (given == 0 && e->bank_m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: no scenarios (the env has no bank)");
-    if (u.traj_steps < 0 || u.traj_steps >= (1 << 30) || (u.traj_steps > 0 && (!u.traj_pos || !u.traj_act)))
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes: traj_steps %d needs both trajectory pointers", u.traj_steps);
-    if (u.max_steps < 0 || u.max_workgroups < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: max_steps / max_workgroups < 0");
-    if ((((uintptr_t)u.start_goal) | ((uintptr_t)u.sub) | ((uintptr_t)u.v0) | ((uintptr_t)u.traj_pos)) & 7u)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes: misaligned f64 array");
-    if (((uintptr_t)u.nsub) & 3u) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: misaligned nsub");
+    EVAL_TRY(eval_check_common(name, e, u, net->local));
+    EVAL_TRY(eval_check_dqn_net(name, -1, e, net, UAVENV_MFMA_F32));
     HIP_TRY(hipSetDevice(e->cfg.device));
-    hipStream_t s = (hipStream_t)stream;
+    StepArgs a = eval_step_args(e, u);
+    EvalArgs v;
+    memset(&v, 0, sizeof(v));
+    v.local = net->local;
+    v.traj_act = u.traj_steps > 0 ? u.traj_act : nullptr;
+    v.eps = u.eps;
+    v.n2 = net->n_actions + (net->dueling ? 1 : 0);
+    v.dueling = net->dueling;
+    // (the wave slot: the work queue, then the wavefront's 64 packed rows)
+    const size_t lds = eval_run_setup(e, u, v.run, uavq::kSplitF * 4, uavq::kMaxOut * uavq::kHid + uavq::kMaxOut, 64 * kPackedDwords * 4);
+    const void *fn = eval_kernel(e, kernels);
+    int grid = 0;
+    EVAL_TRY(eval_grid(name, e, fn, lds, u.max_workgroups, 1, v.run, &grid));
     if (!e->eval_img) HIP_TRY(hipMalloc((void **)&e->eval_img, 2 * UAVENV_DQN_IMAGE_FLOATS * sizeof(float)));
     UavDqnNet img_net = *net;
     img_net.target = net->local;       // (the image call converts two nets: q_local twice, the first half is used)
     const int rc = uavenv_dqn_split_image(&img_net, e->eval_img, stream);
     if (rc != UAVENV_OK) return fail(rc, "uavenv_eval_episodes: layer-1 image");
-
-    // the env's parameters and world; the scenario set in the bank's place; nothing the step launches own
-    StepArgs a = base_args(e);
-    a.moved_word = nullptr;
-    a.meta = nullptr;
-    a.meta_a1 = nullptr;
-    a.dbg = nullptr;
-    a.block = 256;
-    if (given == 3) {
-        a.bank.start_goal = u.start_goal;
-        a.bank.sub = u.sub;
-        a.bank.nsub = u.nsub;
-        a.bank.m = u.m;
-    }
-    EvalArgs v;
-    memset(&v, 0, sizeof(v));
     v.img = e->eval_img;
-    v.local = net->local;
-    v.v0 = u.v0;
-    v.rec = reinterpret_cast<uint4 *>(u.records);
-    v.traj_pos = u.traj_steps > 0 ? u.traj_pos : nullptr;
-    v.traj_act = u.traj_steps > 0 ? u.traj_act : nullptr;
-    v.seed = u.seed;
-    v.eps = u.eps;
-    v.n = u.n;
-    v.first = u.first;
-    v.max_steps = u.max_steps;
-    v.traj_steps = u.traj_steps;
-    v.n2 = n2;
-    v.dueling = net->dueling;
-    v.img_off = (e->world_bytes + 15) & ~15;
-    v.w2_off = v.img_off + uavq::kSplitF * 4;
-    v.slot_off = (v.w2_off + (uavq::kMaxOut * uavq::kHid + uavq::kMaxOut) * 4 + 15) & ~15;
-    int slot = (int)sizeof(ObsWaveLds);            // the work queue, then (same bytes) the wavefront's 64 packed rows
-    if (slot < 64 * kPackedDwords * 4) slot = 64 * kPackedDwords * 4;
-    v.slot_bytes = (slot + 15) & ~15;
-    const size_t lds = (size_t)v.slot_off + 4 * (size_t)v.slot_bytes;
-    const void *fn = e->mask_bytes == 4 ? reinterpret_cast<const void *>(k_eval_episodes<uint32_t>)
-                                        : reinterpret_cast<const void *>(k_eval_episodes<uint64_t>);
-    if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // grid: as many workgroups as stay resident, at most one per 256 episodes (or max_workgroups)
-    const int want = (int)(((int64_t)u.n + 255) / 256);
-    int grid = want;
-    if (u.max_workgroups > 0) {
-        grid = u.max_workgroups < want ? u.max_workgroups : want;
-    } else {
-        int per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device));
-        const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-        if (resident < grid) grid = (int)resident;
-    }
-    if (grid < 1) grid = 1;
-    v.lanes = grid * 256;
-    // (a lane's next episode is e + lanes in 32-bit arithmetic: the last one taken must still be representable)
-    if ((int64_t)u.n + (int64_t)v.lanes > (int64_t)INT32_MAX)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes: n %d + %d lanes exceeds the episode index range", u.n, v.lanes);
-    if (e->mask_bytes == 4) hipLaunchKernelGGL(k_eval_episodes<uint32_t>, dim3(grid), dim3(256), lds, s, a, v);
-    else hipLaunchKernelGGL(k_eval_episodes<uint64_t>, dim3(grid), dim3(256), lds, s, a, v);
-    HIP_TRY(hipGetLastError());
-    return UAVENV_OK;
+    return eval_launch(fn, grid, 1, lds, stream, a, v);
 }
 
-// uavenv_eval_episodes for an f16-MFMA net on an f16 or packed env (k_eval_episodes_h).  Every refusal comes before anything is
-// allocated or enqueued; the kernel stages fc1 itself, so this entry needs no layer-1 image and allocates nothing at all.
+// uavenv_eval_episodes for an f16-MFMA net on an f16 or packed env (k_eval_episodes_h).  The kernel stages fc1 itself, so this
+// entry needs no layer-1 image and allocates nothing at all.
 int uavenv_eval_episodes_f16(UavEnv *e, const UavDqnNet *net, const UavEvalArgs *args, void *stream)
 {
+    static const char *const name = "uavenv_eval_episodes_f16";
+    static const EvalKernels kernels = {{{reinterpret_cast<const void *>(k_eval_episodes_h<uint64_t>), nullptr},
+                                         {reinterpret_cast<const void *>(k_eval_episodes_h<uint32_t>), nullptr}}};
     if (!e || !net || !args) return fail(UAVENV_EINVAL, "null argument");
     const UavEvalArgs &u = *args;
     if (e->cfg.apf_enabled == 1) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: APF envs are not supported");
     if (e->cfg.obs_dtype != UAVENV_OBS_F16 && e->cfg.obs_dtype != UAVENV_OBS_PACKED)
         return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: needs an env with f16 or packed observation rows");
-    if (!e->have_world) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16 before uavenv_set_buildings");
-    const int n2 = net->n_actions + (net->dueling ? 1 : 0);
-    if (!net->local || net->mfma_dtype != UAVENV_MFMA_F16 || net->w != uavq::kW || net->hid != uavq::kHid || net->n_actions < 2 ||
-        n2 > 4 || net->n_actions != e->cfg.n_actions)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: needs an f16-MFMA net of w %d, hid %d, the env's %d actions, <= 4 outputs",
-                    uavq::kW, uavq::kHid, e->cfg.n_actions);
-    if (u.n <= 0 || u.first < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: n %d, first %d", u.n, u.first);
-    if (!u.records || ((((uintptr_t)u.records) | ((uintptr_t)net->local)) & 15u) != 0)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: records and net->local must be 16-byte aligned device pointers");
-    const int given = (u.start_goal ? 1 : 0) + (u.sub ? 1 : 0) + (u.nsub ? 1 : 0);
-    if (given != 0 && given != 3) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: give all three scenario arrays or none");
-    if (given == 3 && u.m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: m %d", u.m);
-    if (given == 0 && e->bank_m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: no scenarios (the env has no bank)");
-    if (u.traj_steps < 0 || u.traj_steps >= (1 << 30) || (u.traj_steps > 0 && (!u.traj_pos || !u.traj_act)))
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: traj_steps %d needs both trajectory pointers", u.traj_steps);
-    if (u.max_steps < 0 || u.max_workgroups < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: max_steps / max_workgroups < 0");
-    if ((((uintptr_t)u.start_goal) | ((uintptr_t)u.sub) | ((uintptr_t)u.v0) | ((uintptr_t)u.traj_pos)) & 7u)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: misaligned f64 array");
-    if (((uintptr_t)u.nsub) & 3u) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: misaligned nsub");
+    EVAL_TRY(eval_check_common(name, e, u, net->local));
+    EVAL_TRY(eval_check_dqn_net(name, -1, e, net, UAVENV_MFMA_F16));
     HIP_TRY(hipSetDevice(e->cfg.device));
-    hipStream_t s = (hipStream_t)stream;
-
-    // the env's parameters and world; the scenario set in the bank's place; nothing the step launches own
-    StepArgs a = base_args(e);
-    a.moved_word = nullptr;
-    a.meta = nullptr;
-    a.meta_a1 = nullptr;
-    a.dbg = nullptr;
-    a.block = 256;
-    if (given == 3) {
-        a.bank.start_goal = u.start_goal;
-        a.bank.sub = u.sub;
-        a.bank.nsub = u.nsub;
-        a.bank.m = u.m;
-    }
+    StepArgs a = eval_step_args(e, u);
     EvalArgs v;
     memset(&v, 0, sizeof(v));
     v.local = net->local;
-    v.v0 = u.v0;
-    v.rec = reinterpret_cast<uint4 *>(u.records);
-    v.traj_pos = u.traj_steps > 0 ? u.traj_pos : nullptr;
     v.traj_act = u.traj_steps > 0 ? u.traj_act : nullptr;
-    v.seed = u.seed;
     v.eps = u.eps;
-    v.n = u.n;
-    v.first = u.first;
-    v.max_steps = u.max_steps;
-    v.traj_steps = u.traj_steps;
-    v.n2 = n2;
+    v.n2 = net->n_actions + (net->dueling ? 1 : 0);
     v.dueling = net->dueling;
-    v.img_off = (e->world_bytes + 15) & ~15;       // the f16 fc1 tile (+ b1)
-    v.w2_off = v.img_off + uavq::kPolWBytes;
-    v.slot_off = (v.w2_off + (uavq::kMaxOut * uavq::kHid + uavq::kMaxOut) * 4 + 15) & ~15;
-    int slot = (int)sizeof(ObsWaveLds);            // the work queue, then (same bytes) the wavefront's 16-row strip of halves
-    if (slot < 16 * uavq::kPolLdW * 2) slot = 16 * uavq::kPolLdW * 2;
-    v.slot_bytes = (slot + 15) & ~15;
-    const size_t lds = (size_t)v.slot_off + 4 * (size_t)v.slot_bytes;
-    const void *fn = e->mask_bytes == 4 ? reinterpret_cast<const void *>(k_eval_episodes_h<uint32_t>)
-                                        : reinterpret_cast<const void *>(k_eval_episodes_h<uint64_t>);
-    if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // grid: as many workgroups as stay resident, at most one per 256 episodes (or max_workgroups)
-    const int want = (int)(((int64_t)u.n + 255) / 256);
-    int grid = want;
-    if (u.max_workgroups > 0) {
-        grid = u.max_workgroups < want ? u.max_workgroups : want;
-    } else {
-        int per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device));
-        const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-        if (resident < grid) grid = (int)resident;
-    }
-    if (grid < 1) grid = 1;
-    v.lanes = grid * 256;
-    // (a lane's next episode is e + lanes in 32-bit arithmetic: the last one taken must still be representable)
-    if ((int64_t)u.n + (int64_t)v.lanes > (int64_t)INT32_MAX)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: n %d + %d lanes exceeds the episode index range", u.n, v.lanes);
-    if (e->mask_bytes == 4) hipLaunchKernelGGL(k_eval_episodes_h<uint32_t>, dim3(grid), dim3(256), lds, s, a, v);
-    else hipLaunchKernelGGL(k_eval_episodes_h<uint64_t>, dim3(grid), dim3(256), lds, s, a, v);
-    HIP_TRY(hipGetLastError());
-    return UAVENV_OK;
+    // (layer 1: the f16 fc1 tile + b1; the wave slot: the work queue, then the wavefront's 16-row strip of halves)
+    const size_t lds = eval_run_setup(e, u, v.run, uavq::kPolWBytes, uavq::kMaxOut * uavq::kHid + uavq::kMaxOut, 16 * uavq::kPolLdW * 2);
+    const void *fn = eval_kernel(e, kernels);
+    int grid = 0;
+    EVAL_TRY(eval_grid(name, e, fn, lds, u.max_workgroups, 1, v.run, &grid));
+    return eval_launch(fn, grid, 1, lds, stream, a, v);
 }
 
 int uavenv_eval_episodes_sac(UavEnv *e, const UavSacEvalArgs *args, void *stream)
 {
+    static const char *const name = "uavenv_eval_episodes_sac";
+    static const EvalKernels kernels = {{{reinterpret_cast<const void *>(k_eval_episodes_sac<uint64_t, false>),
+                                          reinterpret_cast<const void *>(k_eval_episodes_sac<uint64_t, true>)},
+                                         {reinterpret_cast<const void *>(k_eval_episodes_sac<uint32_t, false>),
+                                          reinterpret_cast<const void *>(k_eval_episodes_sac<uint32_t, true>)}}};
     if (!e || !args) return fail(UAVENV_EINVAL, "null argument");
     const UavSacEvalArgs &u = *args;
-    const bool apf = e->cfg.apf_enabled == 1;
-    if (!e->have_world) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac before uavenv_set_buildings");
-    if (u.n <= 0 || u.first < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: n %d, first %d", u.n, u.first);
+    EVAL_TRY(eval_check_common(name, e, u, nullptr));
     if ((u.n_actors != 1 && u.n_actors != e->cfg.uav_per_env) || u.n_actors > UAVENV_SAC_LOOP_MAX_SLOTS || !u.actors)
         return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: n_actors %d (1 or uav_per_env = %d, at most %d)", u.n_actors,
                     e->cfg.uav_per_env, UAVENV_SAC_LOOP_MAX_SLOTS);
@@ -3382,205 +3287,61 @@ int uavenv_eval_episodes_sac(UavEnv *e, const UavSacEvalArgs *args, void *stream
     if (!std::isfinite(u.action_bound) || u.action_bound <= 0.0f)
         return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: action_bound %g", (double)u.action_bound);
     if (u.mode != UAVENV_EVAL_SAC_MEAN && u.mode != UAVENV_EVAL_SAC_SAMPLE) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: mode %d", u.mode);
-    if (!u.records || (((uintptr_t)u.records) & 15u) != 0)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: records must be a 16-byte aligned device pointer");
-    const int given = (u.start_goal ? 1 : 0) + (u.sub ? 1 : 0) + (u.nsub ? 1 : 0);
-    if (given != 0 && given != 3) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: give all three scenario arrays or none");
-    if (given == 3 && u.m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: m %d", u.m);
-    if (given == 0 && e->bank_m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: no scenarios (the env has no bank)");
-    if (u.traj_steps < 0 || u.traj_steps >= (1 << 30) || (u.traj_steps > 0 && (!u.traj_pos || !u.traj_act)))
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: traj_steps %d needs both trajectory pointers", u.traj_steps);
-    if (u.max_steps < 0 || u.max_workgroups < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: max_steps / max_workgroups < 0");
-    if ((((uintptr_t)u.start_goal) | ((uintptr_t)u.sub) | ((uintptr_t)u.v0) | ((uintptr_t)u.traj_pos)) & 7u)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: misaligned f64 array");
-    if ((((uintptr_t)u.nsub) & 3u) || (((uintptr_t)u.traj_act) & 7u)) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: misaligned nsub / traj_act");
     HIP_TRY(hipSetDevice(e->cfg.device));
-    hipStream_t s = (hipStream_t)stream;
-
-    // the env's parameters and world; the scenario set in the bank's place; nothing the step launches own
-    StepArgs a = base_args(e);
-    a.moved_word = nullptr;
-    a.meta = nullptr;
-    a.meta_a1 = nullptr;
-    a.dbg = nullptr;
-    a.block = 256;
-    if (given == 3) {
-        a.bank.start_goal = u.start_goal;
-        a.bank.sub = u.sub;
-        a.bank.nsub = u.nsub;
-        a.bank.m = u.m;
-    }
+    StepArgs a = eval_step_args(e, u);
     SacEvalArgs v;
     memset(&v, 0, sizeof(v));
     for (int k = 0; k < u.n_actors; ++k) v.actor[k] = u.actors[k];
-    v.v0 = u.v0;
-    v.rec = reinterpret_cast<uint4 *>(u.records);
-    v.traj_pos = u.traj_steps > 0 ? u.traj_pos : nullptr;
     v.traj_act = u.traj_steps > 0 ? u.traj_act : nullptr;
-    v.seed = u.seed;
     v.bound = u.action_bound;
     v.mode = u.mode;
     v.n_actors = u.n_actors;
-    v.n = u.n;
-    v.first = u.first;
-    v.max_steps = u.max_steps;
-    v.traj_steps = u.traj_steps;
-    v.img_off = (e->world_bytes + 15) & ~15;
-    v.w2_off = v.img_off + uavq::kSplitF * 4;
-    v.slot_off = (v.w2_off + (4 * uavq::kHid + 4) * 4 + 15) & ~15;
-    int slot = (int)sizeof(ObsWaveLds);            // the work queue, then (same bytes) the wavefront's 64 packed rows
-    if (slot < 64 * kPackedDwords * 4) slot = 64 * kPackedDwords * 4;
-    v.slot_bytes = (slot + 15) & ~15;
-    const size_t lds = (size_t)v.slot_off + 4 * (size_t)v.slot_bytes;
-    const bool m32 = e->mask_bytes == 4;
-    const void *fn = apf ? (m32 ? reinterpret_cast<const void *>(k_eval_episodes_sac<uint32_t, true>)
-                                : reinterpret_cast<const void *>(k_eval_episodes_sac<uint64_t, true>))
-                         : (m32 ? reinterpret_cast<const void *>(k_eval_episodes_sac<uint32_t, false>)
-                                : reinterpret_cast<const void *>(k_eval_episodes_sac<uint64_t, false>));
-    if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // grid.x, per actor: as many workgroups as stay resident beside the other actors', at most one per 256 of its episodes
-    const int64_t per_actor = ((int64_t)u.n + u.n_actors - 1) / u.n_actors;
-    const int want = (int)((per_actor + 255) / 256);
-    int grid = want;
-    if (u.max_workgroups > 0) {
-        grid = u.max_workgroups < want ? u.max_workgroups : want;
-    } else {
-        int per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device));
-        const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1) / u.n_actors;
-        if (resident < grid) grid = (int)(resident > 0 ? resident : 1);
-    }
-    if (grid < 1) grid = 1;
-    const int64_t lanes = (int64_t)grid * u.n_actors * 256;
-    // (a lane's next episode is e + lanes in 32-bit arithmetic: the last one taken must still be representable)
-    if ((int64_t)u.n + lanes > (int64_t)INT32_MAX)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_sac: n %d + %lld lanes exceeds the episode index range", u.n, (long long)lanes);
-    v.lanes = (int32_t)lanes;
-    if (apf) {
-        // one private [K][3] list per resident lane; the env's own lists (e->st.sub) stay as they are.  (hipFree synchronises the
-        // device: an earlier evaluation still in flight has finished with the old workspace before it goes.)
-        if (e->eval_sub_lanes < lanes) {
-            (void)hipFree(e->eval_sub);
-            e->eval_sub = nullptr;
-            e->eval_sub_lanes = 0;
-            HIP_TRY(hipMalloc((void **)&e->eval_sub, (size_t)lanes * (size_t)a.K * 3 * sizeof(double)));
-            e->eval_sub_lanes = lanes;
-        }
-        a.st.sub = e->eval_sub;
-    }
-    const dim3 g3((unsigned)grid, (unsigned)u.n_actors);
-    if (apf) {
-        if (m32) hipLaunchKernelGGL((k_eval_episodes_sac<uint32_t, true>), g3, dim3(256), lds, s, a, v);
-        else hipLaunchKernelGGL((k_eval_episodes_sac<uint64_t, true>), g3, dim3(256), lds, s, a, v);
-    } else {
-        if (m32) hipLaunchKernelGGL((k_eval_episodes_sac<uint32_t, false>), g3, dim3(256), lds, s, a, v);
-        else hipLaunchKernelGGL((k_eval_episodes_sac<uint64_t, false>), g3, dim3(256), lds, s, a, v);
-    }
-    HIP_TRY(hipGetLastError());
-    return UAVENV_OK;
+    // (layer 2: fc_mu | fc_std [4][64] + their biases; the wave slot: the work queue, then the wavefront's 64 packed rows)
+    const size_t lds = eval_run_setup(e, u, v.run, uavq::kSplitF * 4, 4 * uavq::kHid + 4, 64 * kPackedDwords * 4);
+    const void *fn = eval_kernel(e, kernels);
+    int grid = 0;
+    EVAL_TRY(eval_grid(name, e, fn, lds, u.max_workgroups, u.n_actors, v.run, &grid));
+    if (e->cfg.apf_enabled == 1) EVAL_TRY(eval_apf_workspace(e, a, v.run.lanes));
+    return eval_launch(fn, grid, u.n_actors, lds, stream, a, v);
 }
 
 int uavenv_eval_episodes_slots(UavEnv *e, const UavDqnNet *const *nets, int32_t n_nets, const UavEvalArgs *args, void *stream)
 {
+    static const char *const name = "uavenv_eval_episodes_slots";
+    static const EvalKernels kernels = {{{reinterpret_cast<const void *>(k_eval_episodes_slots<uint64_t, false>),
+                                          reinterpret_cast<const void *>(k_eval_episodes_slots<uint64_t, true>)},
+                                         {reinterpret_cast<const void *>(k_eval_episodes_slots<uint32_t, false>),
+                                          reinterpret_cast<const void *>(k_eval_episodes_slots<uint32_t, true>)}}};
     if (!e || !nets || !args) return fail(UAVENV_EINVAL, "null argument");
     const UavEvalArgs &u = *args;
-    const bool apf = e->cfg.apf_enabled == 1;
-    if (!e->have_world) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots before uavenv_set_buildings");
+    EVAL_TRY(eval_check_common(name, e, u, nullptr));
     if ((n_nets != 1 && n_nets != e->cfg.uav_per_env) || n_nets > UAVENV_SAC_LOOP_MAX_SLOTS)
         return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: n_nets %d (1 or uav_per_env = %d, at most %d)", n_nets, e->cfg.uav_per_env,
                     UAVENV_SAC_LOOP_MAX_SLOTS);
     for (int k = 0; k < n_nets; ++k) {
         const UavDqnNet *net = nets[k];
         if (!net) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: net %d is NULL", k);
-        const int n2k = net->n_actions + (net->dueling ? 1 : 0);
-        if (!net->local || net->mfma_dtype != UAVENV_MFMA_F32 || net->w != uavq::kW || net->hid != uavq::kHid || net->n_actions < 2 ||
-            n2k > 4 || net->n_actions != e->cfg.n_actions)
-            return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: net %d: needs an f32-MFMA net of w %d, hid %d, the env's %d actions, <= 4 outputs",
-                        k, uavq::kW, uavq::kHid, e->cfg.n_actions);
+        EVAL_TRY(eval_check_dqn_net(name, k, e, net, UAVENV_MFMA_F32));
         if ((net->dueling ? 1 : 0) != (nets[0]->dueling ? 1 : 0))
             return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: net %d differs from net 0 in dueling", k);
         if (((uintptr_t)net->local) & 15u)
             return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: net %d: local must be a 16-byte aligned device pointer", k);
     }
-    const int n2 = nets[0]->n_actions + (nets[0]->dueling ? 1 : 0);
-    if (u.n <= 0 || u.first < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: n %d, first %d", u.n, u.first);
-    if (!u.records || (((uintptr_t)u.records) & 15u) != 0)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: records must be a 16-byte aligned device pointer");
-    const int given = (u.start_goal ? 1 : 0) + (u.sub ? 1 : 0) + (u.nsub ? 1 : 0);
-    if (given != 0 && given != 3) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: give all three scenario arrays or none");
-    if (given == 3 && u.m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: m %d", u.m);
-    if (given == 0 && e->bank_m <= 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: no scenarios (the env has no bank)");
-    if (u.traj_steps < 0 || u.traj_steps >= (1 << 30) || (u.traj_steps > 0 && (!u.traj_pos || !u.traj_act)))
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: traj_steps %d needs both trajectory pointers", u.traj_steps);
-    if (u.max_steps < 0 || u.max_workgroups < 0) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: max_steps / max_workgroups < 0");
-    if ((((uintptr_t)u.start_goal) | ((uintptr_t)u.sub) | ((uintptr_t)u.v0) | ((uintptr_t)u.traj_pos)) & 7u)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: misaligned f64 array");
-    if (((uintptr_t)u.nsub) & 3u) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: misaligned nsub");
     HIP_TRY(hipSetDevice(e->cfg.device));
-    hipStream_t s = (hipStream_t)stream;
-
-    // the env's parameters and world; the scenario set in the bank's place; nothing the step launches own
-    StepArgs a = base_args(e);
-    a.moved_word = nullptr;
-    a.meta = nullptr;
-    a.meta_a1 = nullptr;
-    a.dbg = nullptr;
-    a.block = 256;
-    if (given == 3) {
-        a.bank.start_goal = u.start_goal;
-        a.bank.sub = u.sub;
-        a.bank.nsub = u.nsub;
-        a.bank.m = u.m;
-    }
+    StepArgs a = eval_step_args(e, u);
     SlotsEvalArgs v;
     memset(&v, 0, sizeof(v));
     for (int k = 0; k < n_nets; ++k) v.local[k] = nets[k]->local;
-    v.v0 = u.v0;
-    v.rec = reinterpret_cast<uint4 *>(u.records);
-    v.traj_pos = u.traj_steps > 0 ? u.traj_pos : nullptr;
     v.traj_act = u.traj_steps > 0 ? u.traj_act : nullptr;
-    v.seed = u.seed;
     v.eps = u.eps;
     v.n_nets = n_nets;
-    v.n = u.n;
-    v.first = u.first;
-    v.max_steps = u.max_steps;
-    v.traj_steps = u.traj_steps;
-    v.n2 = n2;
+    v.n2 = nets[0]->n_actions + (nets[0]->dueling ? 1 : 0);
     v.dueling = nets[0]->dueling;
-    v.img_off = (e->world_bytes + 15) & ~15;
-    v.w2_off = v.img_off + uavq::kSplitF * 4;
-    v.slot_off = (v.w2_off + (uavq::kMaxOut * uavq::kHid + uavq::kMaxOut) * 4 + 15) & ~15;
-    int slot = (int)sizeof(ObsWaveLds);            // the work queue, then (same bytes) the wavefront's 64 packed rows
-    if (slot < 64 * kPackedDwords * 4) slot = 64 * kPackedDwords * 4;
-    v.slot_bytes = (slot + 15) & ~15;
-    const size_t lds = (size_t)v.slot_off + 4 * (size_t)v.slot_bytes;
-    const bool m32 = e->mask_bytes == 4;
-    const void *fn = apf ? (m32 ? reinterpret_cast<const void *>(k_eval_episodes_slots<uint32_t, true>)
-                                : reinterpret_cast<const void *>(k_eval_episodes_slots<uint64_t, true>))
-                         : (m32 ? reinterpret_cast<const void *>(k_eval_episodes_slots<uint32_t, false>)
-                                : reinterpret_cast<const void *>(k_eval_episodes_slots<uint64_t, false>));
-    if (lds > 65536) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // grid.x, per net: as many workgroups as stay resident beside the other nets', at most one per 256 of its episodes
-    const int64_t per_net = ((int64_t)u.n + n_nets - 1) / n_nets;
-    const int want = (int)((per_net + 255) / 256);
-    int grid = want;
-    if (u.max_workgroups > 0) {
-        grid = u.max_workgroups < want ? u.max_workgroups : want;
-    } else {
-        int per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device));
-        const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1) / n_nets;
-        if (resident < grid) grid = (int)(resident > 0 ? resident : 1);
-    }
-    if (grid < 1) grid = 1;
-    const int64_t lanes = (int64_t)grid * n_nets * 256;
-    // (a lane's next episode is e + lanes in 32-bit arithmetic: the last one taken must still be representable)
-    if ((int64_t)u.n + lanes > (int64_t)INT32_MAX)
-        return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: n %d + %lld lanes exceeds the episode index range", u.n, (long long)lanes);
-    v.lanes = (int32_t)lanes;
+    // (the wave slot: the work queue, then the wavefront's 64 packed rows)
+    const size_t lds = eval_run_setup(e, u, v.run, uavq::kSplitF * 4, uavq::kMaxOut * uavq::kHid + uavq::kMaxOut, 64 * kPackedDwords * 4);
+    const void *fn = eval_kernel(e, kernels);
+    int grid = 0;
+    EVAL_TRY(eval_grid(name, e, fn, lds, u.max_workgroups, n_nets, v.run, &grid));
     // the nets' layer-1 images, two per image call (nets 2k and 2k + 1; the last net twice when n_nets is odd), in a buffer of this
     // entry's own.  (hipFree synchronises the device: an earlier evaluation still in flight has finished with the old buffer.)
     const int pairs = (n_nets + 1) / 2;
@@ -3591,14 +3352,7 @@ int uavenv_eval_episodes_slots(UavEnv *e, const UavDqnNet *const *nets, int32_t 
         HIP_TRY(hipMalloc((void **)&e->eval_slot_img, (size_t)(2 * pairs) * UAVENV_DQN_IMAGE_FLOATS * sizeof(float)));
         e->eval_slot_imgs = 2 * pairs;
     }
-    if (apf && e->eval_sub_lanes < lanes) {
-        // one private [K][3] list per resident lane, in the workspace uavenv_eval_episodes_sac uses; the env's own lists stay as they are
-        (void)hipFree(e->eval_sub);
-        e->eval_sub = nullptr;
-        e->eval_sub_lanes = 0;
-        HIP_TRY(hipMalloc((void **)&e->eval_sub, (size_t)lanes * (size_t)a.K * 3 * sizeof(double)));
-        e->eval_sub_lanes = lanes;
-    }
+    if (e->cfg.apf_enabled == 1) EVAL_TRY(eval_apf_workspace(e, a, v.run.lanes));
     for (int k = 0; k < pairs; ++k) {
         UavDqnNet img_net = *nets[2 * k];
         img_net.target = nets[2 * k + 1 < n_nets ? 2 * k + 1 : 2 * k]->local;
@@ -3606,17 +3360,7 @@ int uavenv_eval_episodes_slots(UavEnv *e, const UavDqnNet *const *nets, int32_t 
         if (rc != UAVENV_OK) return fail(rc, "uavenv_eval_episodes_slots: layer-1 image");
     }
     v.img = e->eval_slot_img;
-    if (apf) a.st.sub = e->eval_sub;
-    const dim3 g3((unsigned)grid, (unsigned)n_nets);
-    if (apf) {
-        if (m32) hipLaunchKernelGGL((k_eval_episodes_slots<uint32_t, true>), g3, dim3(256), lds, s, a, v);
-        else hipLaunchKernelGGL((k_eval_episodes_slots<uint64_t, true>), g3, dim3(256), lds, s, a, v);
-    } else {
-        if (m32) hipLaunchKernelGGL((k_eval_episodes_slots<uint32_t, false>), g3, dim3(256), lds, s, a, v);
-        else hipLaunchKernelGGL((k_eval_episodes_slots<uint64_t, false>), g3, dim3(256), lds, s, a, v);
-    }
-    HIP_TRY(hipGetLastError());
-    return UAVENV_OK;
+    return eval_launch(fn, grid, n_nets, lds, stream, a, v);
 }
 
 int uavenv_eval_noise_fill(uint64_t seed, int32_t n, int32_t steps, float *out_dev, void *stream)

@@ -91,6 +91,38 @@ def _check_scenarios(scenarios, K):
     return m
 
 
+def _prepare(env, a, n, T, m, scenarios, first, seed, max_steps, v0, max_workgroups, act_tail, act_fill, act_dtype):
+    """What evaluate_policy and evaluate_sac_policy share once their checks have passed: the v0 and scenario tensors on the env's
+    device, the records and the trajectory tensors (actions [n, T, *act_tail] of act_dtype, filled with act_fill), and the
+    common fields of the argument struct `a` (UavEvalArgs or UavSacEvalArgs).  -> (records, pos, act, keep): keep holds what
+    the launch reads and nothing else references."""
+    import torch
+    dev = env.device
+    if v0 is not None:
+        v0 = torch.as_tensor(v0, dtype=torch.float64, device=dev).contiguous()
+    if scenarios is not None:
+        sg = torch.as_tensor(scenarios[0], dtype=torch.float64, device=dev).contiguous()
+        sub = torch.as_tensor(scenarios[1], dtype=torch.float64, device=dev).contiguous()
+        ns = torch.as_tensor(scenarios[2], dtype=torch.int32, device=dev).contiguous()
+    records = torch.zeros((n, _lib.EVAL_RECORD_BYTES), dtype=torch.uint8, device=dev)
+    pos = act = None
+    if T > 0:
+        pos = torch.full((n, T + 1, 3), float("nan"), dtype=torch.float64, device=dev)
+        act = torch.full((n, T) + tuple(act_tail), act_fill, dtype=act_dtype, device=dev)
+    a.n, a.first = n, int(first)
+    if scenarios is not None:
+        a.start_goal, a.sub, a.nsub, a.m = sg.data_ptr(), sub.data_ptr(), ns.data_ptr(), m
+    a.max_steps = int(max_steps)
+    a.v0 = None if v0 is None else v0.data_ptr()
+    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.traj_steps = T
+    a.records = records.data_ptr()
+    a.traj_pos = None if pos is None else pos.data_ptr()
+    a.traj_act = None if act is None else act.data_ptr()
+    a.max_workgroups = int(max_workgroups)
+    return records, pos, act, (v0, scenarios if scenarios is None else (sg, sub, ns))
+
+
 def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int = 0, seed: int = 0, eps: float = 0.0,
                     max_steps: int = 0, v0=None, trajectory_steps: int = 0, max_workgroups: int = 0) -> EvalResult:
     """n_episodes greedy episodes of learner.q_local (a FusedDQNLearner) on env (a VecPathPlanEnv, APF on or off).
@@ -132,31 +164,9 @@ def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int
     if f16 and env.obs_code not in (_lib.OBS_F16, _lib.OBS_PACKED):
         raise ValueError("an f16-MFMA learner is evaluated on an env with f16 or packed rows (what it acts on), not f32 rows")
     import torch
-    dev = env.device
-    if v0 is not None:
-        v0 = torch.as_tensor(v0, dtype=torch.float64, device=dev).contiguous()
-    if scenarios is not None:
-        sg = torch.as_tensor(scenarios[0], dtype=torch.float64, device=dev).contiguous()
-        sub = torch.as_tensor(scenarios[1], dtype=torch.float64, device=dev).contiguous()
-        ns = torch.as_tensor(scenarios[2], dtype=torch.int32, device=dev).contiguous()
-    records = torch.zeros((n, _lib.EVAL_RECORD_BYTES), dtype=torch.uint8, device=dev)
-    pos = act = None
-    if T > 0:
-        pos = torch.full((n, T + 1, 3), float("nan"), dtype=torch.float64, device=dev)
-        act = torch.full((n, T), -1, dtype=torch.int8, device=dev)
     a = _lib.UavEvalArgs()
-    a.n, a.first = n, int(first)
-    if scenarios is not None:
-        a.start_goal, a.sub, a.nsub, a.m = sg.data_ptr(), sub.data_ptr(), ns.data_ptr(), m
-    a.max_steps = int(max_steps)
-    a.v0 = None if v0 is None else v0.data_ptr()
-    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    records, pos, act, keep = _prepare(env, a, n, T, m, scenarios, first, seed, max_steps, v0, max_workgroups, (), -1, torch.int8)
     a.eps = float(eps)
-    a.traj_steps = T
-    a.records = records.data_ptr()
-    a.traj_pos = None if pos is None else pos.data_ptr()
-    a.traj_act = None if act is None else act.data_ptr()
-    a.max_workgroups = int(max_workgroups)
     if f16:
         _lib.check(env.lib.uavenv_eval_episodes_f16(env._h, C.byref(learner.net), C.byref(a), env._stream()), "uavenv_eval_episodes_f16")
     elif as_list or int(env.cfg.apf_enabled) == 1:
@@ -165,7 +175,7 @@ def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int
     else:
         _lib.check(env.lib.uavenv_eval_episodes(env._h, C.byref(learner.net), C.byref(a), env._stream()), "uavenv_eval_episodes")
     res = EvalResult(records, pos, act)
-    res._keep = (v0, scenarios if scenarios is None else (sg, sub, ns), ls)   # alive until the launch has read them
+    res._keep = keep + (ls,)           # alive until the launch has read them
     return res
 
 
@@ -200,37 +210,16 @@ def evaluate_sac_policy(env, learners, n_episodes: int, *, scenarios=None, first
     if len(ls) != 1 and len(ls) != env.uav_per_env:
         raise ValueError(f"one learner or uav_per_env = {env.uav_per_env} of them (got {len(ls)})")
     import torch
-    dev = env.device
-    if v0 is not None:
-        v0 = torch.as_tensor(v0, dtype=torch.float64, device=dev).contiguous()
-    if scenarios is not None:
-        sg = torch.as_tensor(scenarios[0], dtype=torch.float64, device=dev).contiguous()
-        sub = torch.as_tensor(scenarios[1], dtype=torch.float64, device=dev).contiguous()
-        ns = torch.as_tensor(scenarios[2], dtype=torch.int32, device=dev).contiguous()
-    records = torch.zeros((n, _lib.EVAL_RECORD_BYTES), dtype=torch.uint8, device=dev)
-    pos = act = None
-    if T > 0:
-        pos = torch.full((n, T + 1, 3), float("nan"), dtype=torch.float64, device=dev)
-        act = torch.full((n, T, 2), float("nan"), dtype=torch.float32, device=dev)
     a = _lib.UavSacEvalArgs()
-    a.n, a.first = n, int(first)
-    if scenarios is not None:
-        a.start_goal, a.sub, a.nsub, a.m = sg.data_ptr(), sub.data_ptr(), ns.data_ptr(), m
-    a.max_steps = int(max_steps)
-    a.v0 = None if v0 is None else v0.data_ptr()
-    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    records, pos, act, keep = _prepare(env, a, n, T, m, scenarios, first, seed, max_steps, v0, max_workgroups, (2,), float("nan"),
+                                       torch.float32)
     actors = (C.c_void_p * len(ls))(*[L._blocks[0].data_ptr() for L in ls])
     a.actors, a.n_actors = actors, len(ls)
     a.action_bound = bound
     a.mode = SAC_MODES[mode]
-    a.traj_steps = T
-    a.records = records.data_ptr()
-    a.traj_pos = None if pos is None else pos.data_ptr()
-    a.traj_act = None if act is None else act.data_ptr()
-    a.max_workgroups = int(max_workgroups)
     _lib.check(env.lib.uavenv_eval_episodes_sac(env._h, C.byref(a), env._stream()), "uavenv_eval_episodes_sac")
     res = EvalResult(records, pos, act)
-    res._keep = (v0, scenarios if scenarios is None else (sg, sub, ns), ls)   # alive until the launch has read them
+    res._keep = keep + (ls,)           # alive until the launch has read them
     return res
 
 

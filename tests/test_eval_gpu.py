@@ -272,6 +272,7 @@ def test_refusals_leave_the_env_unchanged():
     assert call(net=wide) == _lib.EINVAL
     L5 = FusedDQNLearner(dict(PARAM, NetWork="VAnet2", output="5"), "dueling", device=DEV)
     assert call(net=L5.net) == _lib.EINVAL                                               # 6 layer-2 outputs
+    assert call(n=2 ** 31 - 100) == _lib.EINVAL                                          # n + the grid's lanes > INT32_MAX: the last refusal
     torch.cuda.synchronize()
     assert _state_bytes(env) == before and env.lib.uavenv_tick(env._h) == tick
     env.close()
