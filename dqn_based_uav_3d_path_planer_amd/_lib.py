@@ -49,6 +49,7 @@ SYMBOLS = (
     "uavenv_per_fill_frame_slots", "uavenv_per_rebuild_slots", "uavenv_per_sample_slots", "uavenv_per_weights_slots",
     "uavenv_per_set_f32_slots_gated", "uavenv_dqn_grad_slots_w", "uavenv_dqn_slots_loop_set_per", "uavenv_dqn_slots_loop_get_per",
     "uavenv_eval_episodes_f16",
+    "uavenv_scripted_act", "uavenv_eval_episodes_scripted",
 )
 SAC_CRITIC_IN, SAC_ACTOR_PARAMS, SAC_CRITIC_PARAMS, SAC_ACTOR_STRIDE, SAC_CRITIC_STRIDE = 102, 6724, 10882, 6728, 21768
 
@@ -108,6 +109,14 @@ class UavSacEvalArgs(C.Structure):
                 ("action_bound", C.c_float), ("mode", C.c_int32), ("traj_steps", C.c_int32), ("records", C.c_void_p),
                 ("traj_pos", C.c_void_p), ("traj_act", C.c_void_p), ("max_workgroups", C.c_int32),
                 ("reserved0", C.c_int32)]
+
+
+# the scripted baseline (include/uavenv.h: uavenv_scripted_act, uavenv_eval_episodes_scripted)
+SCRIPTED_MAX_LOOKAHEAD, SCRIPTED_MAX_STEER_CANDIDATES, SCRIPTED_MAX_INDEX_ACTIONS = 16, 17, 32
+
+
+class UavScriptedPolicy(C.Structure):
+    _fields_ = [("action_kind", C.c_int32), ("candidates", C.c_int32), ("lookahead", C.c_int32), ("reserved0", C.c_int32)]
 
 
 class UavPer(C.Structure):
@@ -471,6 +480,10 @@ def load() -> C.CDLL:
     lib.uavenv_eval_episodes_slots.argtypes = [vp, C.POINTER(C.POINTER(UavDqnNet)), i32, C.POINTER(UavEvalArgs), vp]
     lib.uavenv_eval_episodes_sac.restype = C.c_int
     lib.uavenv_eval_episodes_sac.argtypes = [vp, C.POINTER(UavSacEvalArgs), vp]
+    lib.uavenv_scripted_act.restype = C.c_int
+    lib.uavenv_scripted_act.argtypes = [vp, C.POINTER(UavScriptedPolicy), vp, vp]
+    lib.uavenv_eval_episodes_scripted.restype = C.c_int
+    lib.uavenv_eval_episodes_scripted.argtypes = [vp, C.POINTER(UavScriptedPolicy), C.POINTER(UavEvalArgs), vp]
     lib.uavenv_eval_noise_fill.restype = C.c_int
     lib.uavenv_eval_noise_fill.argtypes = [u64, i32, i32, vp, vp]
     lib.uavenv_dqn_act_slots.restype = C.c_int

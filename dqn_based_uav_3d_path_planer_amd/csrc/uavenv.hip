@@ -1637,6 +1637,8 @@ __global__ void k_get_state(StepArgs a, int first, int count, double *__restrict
 //   eval_obs_row (all four)  eval_stage_w2 (DQN: plain, _h, _slots)  eval_forward_f32 (plain, _sac, _slots; _h has its own strip loop)
 //   eval_dqn_action (DQN)    eval_step, eval_episode_end, eval_install, eval_store_record (all four)
 // The trajectory's action store stays in each kernel (int8 or float2), between eval_step and eval_episode_end, which moves L.e.
+// A fifth kernel, k_eval_episodes_scripted (the scripted baseline, further down), has no forward and no row: its prelude stages the
+// world only, and its loop is eval_install, the policy function, eval_step, eval_episode_end; eval_eps_action serves it and the DQN three.
 // ------------------------------------------------------------------------------------------------
 // the per-run fields of every evaluation kernel's argument block (EvalArgs, SacEvalArgs, SlotsEvalArgs embed one as `run`)
 struct EvalRun {
@@ -1786,8 +1788,19 @@ __device__ __forceinline__ void eval_forward_f32(const uavq::W1Split &W1, const 
     wave_lds_sync();                                                 // the rows are read: the next iteration's queue may take the bytes
 }
 
-// The action of a DQN lane: the acting kernels' greedy branch (first maximum, strict >); eps > 0: a uniform action where the
-// 24-bit draw of Philox (seed; e, step, 0, 0xe75f) is < eps.
+// The exploration draw of an index policy (the DQN kernels' and the scripted baseline's): eps > 0: a uniform action in the place of
+// `act` where the 24-bit draw of Philox (seed; e, step, 0, 0xe75f) is < eps.
+__device__ __forceinline__ int eval_eps_action(int act, int A, float eps, uint64_t seed, int e, int step)
+{
+    if (eps > 0.0f) {
+        const uint4 rn = philox4x32_10(make_uint4((uint32_t)e, (uint32_t)step, 0u, 0xe75fu), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+        const float u = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
+        if (u < eps) act = (int)(((uint64_t)rn.y * (uint64_t)A) >> 32);
+    }
+    return act;
+}
+
+// The action of a DQN lane: the acting kernels' greedy branch (first maximum, strict >), then eval_eps_action.
 __device__ __forceinline__ int eval_dqn_action(const float (&q)[4], int A, float eps, uint64_t seed, int e, int step)
 {
     int act = 0;
@@ -1795,12 +1808,7 @@ __device__ __forceinline__ int eval_dqn_action(const float (&q)[4], int A, float
 #pragma unroll
     for (int k = 1; k < 4; ++k)
         if (k < A && q[k] > bq) { bq = q[k]; act = k; }
-    if (eps > 0.0f) {
-        const uint4 rn = philox4x32_10(make_uint4((uint32_t)e, (uint32_t)step, 0u, 0xe75fu), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-        const float u = (float)(rn.x >> 8) * (1.0f / 16777216.0f);
-        if (u < eps) act = (int)(((uint64_t)rn.y * (uint64_t)A) >> 32);
-    }
-    return act;
+    return eval_eps_action(act, A, eps, seed, e, step);
 }
 
 // update_PathPlan (UAV.py:397-513, step_agent's pieces) of episode L.e with the decoded action a0, and the episode's accounting.
@@ -2131,6 +2139,131 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_slots(StepArgs a, Slot
                 v.traj_act[(size_t)L.e * run.traj_steps + L.steps - 1] = (int8_t)act;
             install = eval_episode_end(run, g, L, info, j);
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The scripted baseline (uavenv_scripted_act, uavenv_eval_episodes_scripted): sub-goal pursuit with look-ahead, a controller that
+// learns nothing, flown through the same missions by the same loop.  The policy reads what an Agent holds in registers and the
+// LDS world: no observation row, no forward, no HBM.  Candidate steers k = 0 .. C - 1: the index table -1 + 2k / (A - 1)
+// (decode_action) or, for the steer kind, the f32 value of -1 + 2k / (C - 1) read back as uavenv_step reads an f32 steer.
+//   n_rem == 0: candidate C / 2 (the step's empty-list guard ends the episode).
+//   s* = clamp(wrap(calculate_angle(sub0 - pos) - heading) / Steering_angle, -1, 1) with wrap into (-pi, pi]; cost_k = |steer_k - s*|.
+//   Candidate k is blocked where Threaten_rate(pos + t V_k) = 1 for some t = 1 .. H; V_k is the V_vector step_pre sets for steer_k
+//   (the same expression, the same Calc_V clamp: the t = 1 probe is bit for bit the point the step moves to).
+//   The unblocked candidate of least cost, the lower k on equal cost; all blocked: the least cost among those whose t = 1 probe is
+//   free; none of those either: the least cost overall.
+// So with H >= 1 a step takes the collision branch (UAV.py:425-428) only when every candidate's t = 1 probe was blocked.
+// ------------------------------------------------------------------------------------------------
+// wavefronts per SIMD the episode kernel is built for (measured: profiles/eval_scripted_resource_usage.txt)
+#ifndef UAVENV_SCRIPTED_WAVES
+#define UAVENV_SCRIPTED_WAVES 2
+#endif
+struct ScriptedPolicy {
+    int32_t kind;                      // UAVENV_ACT_INDEX_I32 | UAVENV_ACT_STEER_F32
+    int32_t C, H;                      // candidates (index kind: the env's n_actions), look-ahead steps
+};
+
+__device__ __forceinline__ double scripted_steer(const ScriptedPolicy &p, int k)
+{
+    if (p.kind == UAVENV_ACT_INDEX_I32) return decode_action(RawAction{(uint32_t)k, 0u}, UAVENV_ACT_INDEX_I32, p.C);
+    const float s = (float)(-1.0 + 2.0 * (double)k / (double)(p.C - 1));
+    return decode_action(RawAction{__float_as_uint(s), 0u}, UAVENV_ACT_STEER_F32, p.C);
+}
+
+template <typename MaskT>
+__device__ __forceinline__ int scripted_candidate(const StepArgs &a, const WorldLds<MaskT> &w, const ScriptedPolicy &p, const Agent &g)
+{
+    const ObsIn &o = g.o;
+    if (o.n_rem == 0) return p.C / 2;
+    double err = angle_of<true>(o.s0x - o.px, o.s0y - o.py) - g.head;
+    if (err > kPi) err -= kTwoPi;
+    if (err <= -kPi) err += kTwoPi;
+    double want = err / a.steer;
+    want = want < -1.0 ? -1.0 : (want > 1.0 ? 1.0 : want);
+    int best = -1, best_next = -1, best_any = 0;                    // least cost among: the unblocked, those free at t = 1, all
+    double cost_best = 0.0, cost_next = 0.0, cost_any = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < p.C; ++k) {
+        const double sk = scripted_steer(p, k);
+        const double cost = fabs(sk - want);
+        int blocked = 0, hit_next = 0;
+        if (p.H > 0) {
+            const double seta_new = g.head + sk * a.steer;          // step_pre :411, :414-417
+            double sn, cs;
+            sincos(seta_new, &sn, &cs);
+            double vx = a.max_v * cs, vy = a.max_v * sn;
+            (void)calc_v(vx, vy, a.max_v);
+            hit_next = blocked = probe(w, o.px + vx, o.py + vy, o.pz);   // (t = 1: 1.0 * v is v)
+#pragma unroll 1
+            for (int t = 2; t <= p.H && !blocked; ++t) blocked = probe(w, o.px + (double)t * vx, o.py + (double)t * vy, o.pz);
+        }
+        if (k == 0 || cost < cost_any) { cost_any = cost; best_any = k; }
+        if (!hit_next && (best_next < 0 || cost < cost_next)) { cost_next = cost; best_next = k; }
+        if (!blocked && (best < 0 || cost < cost_best)) { cost_best = cost; best = k; }
+    }
+    return best >= 0 ? best : (best_next >= 0 ? best_next : best_any);
+}
+
+// the act launch alone: one lane per agent, its candidate as the int32 index or the f32 steer uavenv_step reads.  A done agent
+// gets the middle candidate.  Reads the env, writes actions_out only.
+template <typename MaskT>
+__global__ void __launch_bounds__(256) k_scripted_act(StepArgs a, ScriptedPolicy p, uint32_t *__restrict__ out)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const WorldLds<MaskT> w = stage_world<MaskT>(smem, a);
+    for (int i = blockIdx.x * a.block + threadIdx.x; i < a.N; i += gridDim.x * a.block) {
+        Agent g;
+        load_agent(a.st, i, g);
+        unpack_flags(g);
+        const int k = g.done ? p.C / 2 : scripted_candidate(a, w, p, g);
+        out[i] = p.kind == UAVENV_ACT_INDEX_I32 ? (uint32_t)k : __float_as_uint((float)scripted_steer(p, k));
+    }
+}
+
+// Whole episodes of the scripted baseline (uavenv_eval_episodes_scripted): the fifth episode kernel.  Staging: the world only, by
+// LDS-DMA from all four wavefronts.  The loop is eval_install -> scripted_candidate -> eval_step -> the trajectory's action ->
+// eval_episode_end: no image, no fc2, no wave slot, no observation row, no forward.  One grid slice; slot j = e mod U; APF as
+// k_eval_episodes_slots (the lane's own list in the evaluation workspace).  The trajectory's action plane is int8 indices for the
+// index kind and one f32 steer per step for the steer kind (v.traj_act is the caller's pointer either way).
+struct ScriptedEvalArgs {
+    EvalRun run;
+    void *traj_act;                    // nullable: int8 [n][traj_steps] (index kind) or float [n][traj_steps] (steer kind)
+    float eps;                         // index kind only
+    ScriptedPolicy pol;
+};
+
+template <typename MaskT, bool APF>
+__global__ void __launch_bounds__(256, UAVENV_SCRIPTED_WAVES) k_eval_episodes_scripted(StepArgs a, ScriptedEvalArgs v)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int tid = (int)threadIdx.x;
+    const EvalRun &run = v.run;
+    const ScriptedPolicy &p = v.pol;
+    stage_copy_glds(smem, a, wv, 4);                                 // ---- staging, once per workgroup: the world by LDS-DMA
+    Agent g = {};
+    EvalLane L = {};
+    const int li = (int)blockIdx.x * 256 + tid;                      // resident lane: its sub-goal list (APF)
+    L.e = li;                                                        // this lane's first episode (installed at the loop's top)
+    bool install = true;
+    __syncthreads();                                                 // world staged
+    const WorldLds<MaskT> w = world_view<MaskT>(smem, a);
+    for (;;) {
+        if (install) eval_install<APF>(a, run, g, L, li);            // (one call site: the installation is inlined once)
+        install = false;
+        if (L.e >= run.n) break;                                     // (no wave-collective step: a lane without episodes leaves)
+        int k = scripted_candidate(a, w, p, g);
+        if (p.kind == UAVENV_ACT_INDEX_I32) k = eval_eps_action(k, p.C, v.eps, run.seed, L.e, L.steps);
+        const double a0 = scripted_steer(p, k);
+        const int j = L.e % a.U;
+        int info;
+        if (eval_step<MaskT, APF>(a, w, run, a0, j, g, L, info, li)) {
+            const size_t at = (size_t)L.e * run.traj_steps + L.steps - 1;
+            if (p.kind == UAVENV_ACT_INDEX_I32) reinterpret_cast<int8_t *>(v.traj_act)[at] = (int8_t)k;
+            else reinterpret_cast<float *>(v.traj_act)[at] = (float)a0;
+        }
+        install = eval_episode_end(run, g, L, info, j);
     }
 }
 
@@ -3361,6 +3494,77 @@ int uavenv_eval_episodes_slots(UavEnv *e, const UavDqnNet *const *nets, int32_t 
     }
     v.img = e->eval_slot_img;
     return eval_launch(fn, grid, n_nets, lds, stream, a, v);
+}
+
+// what both scripted entries refuse of the policy, and its device form (C resolved to the env's n_actions for the index kind)
+static int scripted_policy_check(const char *name, const UavEnv *e, const UavScriptedPolicy *pol, ScriptedPolicy &p)
+{
+    if (!pol) return fail(UAVENV_EINVAL, "%s: policy is NULL", name);
+    if (!e->have_world) return fail(UAVENV_EINVAL, "%s before uavenv_set_buildings", name);
+    if (pol->action_kind != UAVENV_ACT_INDEX_I32 && pol->action_kind != UAVENV_ACT_STEER_F32)
+        return fail(UAVENV_EINVAL, "%s: action_kind %d (UAVENV_ACT_INDEX_I32 or UAVENV_ACT_STEER_F32)", name, pol->action_kind);
+    if (pol->lookahead < 0 || pol->lookahead > UAVENV_SCRIPTED_MAX_LOOKAHEAD)
+        return fail(UAVENV_EINVAL, "%s: lookahead %d outside 0..%d", name, pol->lookahead, UAVENV_SCRIPTED_MAX_LOOKAHEAD);
+    if (pol->action_kind == UAVENV_ACT_INDEX_I32) {
+        if (pol->candidates != 0) return fail(UAVENV_EINVAL, "%s: candidates must be 0 for the index kind (the env's n_actions)", name);
+        if (e->cfg.n_actions < 2 || e->cfg.n_actions > UAVENV_SCRIPTED_MAX_INDEX_ACTIONS)
+            return fail(UAVENV_EINVAL, "%s: the index kind takes 2..%d actions (the env has %d)", name, UAVENV_SCRIPTED_MAX_INDEX_ACTIONS,
+                        e->cfg.n_actions);
+        p.C = e->cfg.n_actions;
+    } else {
+        if (pol->candidates < 3 || pol->candidates > UAVENV_SCRIPTED_MAX_STEER_CANDIDATES || (pol->candidates & 1) == 0)
+            return fail(UAVENV_EINVAL, "%s: candidates %d (odd, 3..%d)", name, pol->candidates, UAVENV_SCRIPTED_MAX_STEER_CANDIDATES);
+        p.C = pol->candidates;
+    }
+    p.kind = pol->action_kind;
+    p.H = pol->lookahead;
+    return UAVENV_OK;
+}
+
+int uavenv_scripted_act(UavEnv *e, const UavScriptedPolicy *policy, void *actions_out, void *stream)
+{
+    static const char *const name = "uavenv_scripted_act";
+    if (!e || !actions_out) return fail(UAVENV_EINVAL, "uavenv_scripted_act: null argument");
+    ScriptedPolicy p;
+    EVAL_TRY(scripted_policy_check(name, e, policy, p));
+    if (((uintptr_t)actions_out) & 3u) return fail(UAVENV_EINVAL, "uavenv_scripted_act: misaligned actions_out");
+    StepArgs a = base_args(e);
+    a.block = 256;
+    const int want = (e->N + 255) / 256;
+    const int grid = want > 2048 ? 2048 : want;
+    const size_t lds = (size_t)e->world_bytes;
+    hipStream_t s = (hipStream_t)stream;
+    if (e->mask_bytes == 4) hipLaunchKernelGGL((k_scripted_act<uint32_t>), dim3(grid), dim3(256), lds, s, a, p, (uint32_t *)actions_out);
+    else hipLaunchKernelGGL((k_scripted_act<uint64_t>), dim3(grid), dim3(256), lds, s, a, p, (uint32_t *)actions_out);
+    HIP_TRY(hipGetLastError());
+    return UAVENV_OK;
+}
+
+int uavenv_eval_episodes_scripted(UavEnv *e, const UavScriptedPolicy *policy, const UavEvalArgs *args, void *stream)
+{
+    static const char *const name = "uavenv_eval_episodes_scripted";
+    static const EvalKernels kernels = {{{reinterpret_cast<const void *>(k_eval_episodes_scripted<uint64_t, false>),
+                                          reinterpret_cast<const void *>(k_eval_episodes_scripted<uint64_t, true>)},
+                                         {reinterpret_cast<const void *>(k_eval_episodes_scripted<uint32_t, false>),
+                                          reinterpret_cast<const void *>(k_eval_episodes_scripted<uint32_t, true>)}}};
+    if (!e || !args) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_scripted: null argument");
+    const UavEvalArgs &u = *args;
+    ScriptedEvalArgs v;
+    EVAL_TRY(scripted_policy_check(name, e, policy, v.pol));
+    EVAL_TRY(eval_check_common(name, e, u, nullptr));
+    const bool steer = v.pol.kind == UAVENV_ACT_STEER_F32;
+    if (steer && u.eps > 0.0f) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_scripted: eps > 0 needs the index kind");
+    if (steer && (((uintptr_t)u.traj_act) & 3u)) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_scripted: misaligned traj_act (f32 steers)");
+    StepArgs a = eval_step_args(e, u);
+    v.traj_act = u.traj_steps > 0 ? (void *)u.traj_act : nullptr;
+    v.eps = u.eps;
+    eval_run_setup(e, u, v.run, 0, 0, 0);                           // (no layer images, no wave slots: the LDS is the world's)
+    const size_t lds = (size_t)((e->world_bytes + 15) & ~15);
+    const void *fn = eval_kernel(e, kernels);
+    int grid = 0;
+    EVAL_TRY(eval_grid(name, e, fn, lds, u.max_workgroups, 1, v.run, &grid));
+    if (e->cfg.apf_enabled == 1) EVAL_TRY(eval_apf_workspace(e, a, v.run.lanes));
+    return eval_launch(fn, grid, 1, lds, stream, a, v);
 }
 
 int uavenv_eval_noise_fill(uint64_t seed, int32_t n, int32_t steps, float *out_dev, void *stream)

@@ -1,7 +1,8 @@
 """Policy evaluation: whole episodes in one GPU launch -- greedy DQN (csrc/uavenv.hip k_eval_episodes, include/uavenv.h
 uavenv_eval_episodes; an f16-MFMA learner: k_eval_episodes_h, uavenv_eval_episodes_f16; one net per UAV slot and APF envs:
-k_eval_episodes_slots, uavenv_eval_episodes_slots) and the continuous SAC actor, APF on or off (k_eval_episodes_sac,
-uavenv_eval_episodes_sac).
+k_eval_episodes_slots, uavenv_eval_episodes_slots), the continuous SAC actor, APF on or off (k_eval_episodes_sac,
+uavenv_eval_episodes_sac), and the scripted baseline they are held to: sub-goal pursuit with look-ahead, no learning
+(k_eval_episodes_scripted, uavenv_eval_episodes_scripted; its act launch alone: uavenv_scripted_act).
 
 The reference meant to have this (Envs/PathPlan_City.py:349-351 Evaluation_Action, :543-552 run_XML_scene / Load_Scene_FromXML)
 and acts greedily when Is_Train == 0 (Trainer/DuelingDQN_Trainer.py:90).  Episode e flies scenario row (first + e) mod m of a
@@ -221,6 +222,83 @@ def evaluate_sac_policy(env, learners, n_episodes: int, *, scenarios=None, first
     res = EvalResult(records, pos, act)
     res._keep = keep + (ls,)           # alive until the launch has read them
     return res
+
+
+SCRIPTED_KINDS = {"index": _lib.ACT_INDEX_I32, "steer": _lib.ACT_STEER_F32}
+
+
+def _scripted_policy(env, action, candidates, lookahead):
+    """The checked UavScriptedPolicy of (action, candidates, lookahead) for env: action "index" takes the env's n_actions as its
+    candidates (candidates None or 0), "steer" an odd number of f32 steers (default 9).  Reads env.cfg only."""
+    if action not in SCRIPTED_KINDS:
+        raise ValueError(f"action must be one of {sorted(SCRIPTED_KINDS)} (got {action!r})")
+    if isinstance(lookahead, bool) or int(lookahead) != lookahead or not 0 <= lookahead <= _lib.SCRIPTED_MAX_LOOKAHEAD:
+        raise ValueError(f"lookahead must be an integer in 0..{_lib.SCRIPTED_MAX_LOOKAHEAD} (got {lookahead!r})")
+    if action == "index":
+        if candidates not in (None, 0):
+            raise ValueError(f"action='index' takes the env's n_actions as its candidates: leave candidates None (got {candidates!r})")
+        A = int(env.cfg.n_actions)
+        if not 2 <= A <= _lib.SCRIPTED_MAX_INDEX_ACTIONS:
+            raise ValueError(f"action='index' needs an env with 2..{_lib.SCRIPTED_MAX_INDEX_ACTIONS} actions (it has {A})")
+        c = 0
+    else:
+        c = 9 if candidates is None else candidates
+        if isinstance(c, bool) or int(c) != c or not 3 <= c <= _lib.SCRIPTED_MAX_STEER_CANDIDATES or int(c) % 2 == 0:
+            raise ValueError(f"candidates must be an odd integer in 3..{_lib.SCRIPTED_MAX_STEER_CANDIDATES} (got {candidates!r})")
+    pol = _lib.UavScriptedPolicy()
+    pol.action_kind, pol.candidates, pol.lookahead = SCRIPTED_KINDS[action], int(c), int(lookahead)
+    return pol
+
+
+def evaluate_scripted_policy(env, n_episodes: int, *, action: str = "index", candidates=None, lookahead: int = 8, scenarios=None,
+                             first: int = 0, seed: int = 0, eps: float = 0.0, max_steps: int = 0, v0=None,
+                             trajectory_steps: int = 0, max_workgroups: int = 0) -> EvalResult:
+    """n_episodes episodes of the scripted baseline -- sub-goal pursuit with look-ahead, a controller that learns nothing -- on env
+    (a VecPathPlanEnv, APF on or off) in one launch (csrc/uavenv.hip k_eval_episodes_scripted, include/uavenv.h
+    uavenv_eval_episodes_scripted): the yardstick for evaluate_policy / evaluate_sac_policy, on the same missions.
+
+    The policy steers at the current sub-goal (the steer that turns the heading onto its bearing, clamped to [-1, 1]) and takes
+    the nearest candidate steer whose next `lookahead` positions are free; with every candidate blocked, the nearest one.
+    action = "index": the candidates are the env's n_actions discrete steers (what a DQN learner chooses from); actions are
+    [n, T] int8; eps > 0 takes evaluate_policy's uniform draw with probability eps.  action = "steer": `candidates` (odd, 3..17,
+    default 9) f32 steers spread over [-1, 1] (what a SAC actor's component 0 is); actions are [n, T] f32 (NaN past the end);
+    eps must be 0.  The other arguments, the records and the positions are evaluate_policy's.  Enqueued on the current stream."""
+    # every check first: nothing is read from the device or enqueued before the arguments are known to be good
+    _check_args(n_episodes, first, eps, max_steps, trajectory_steps, max_workgroups)
+    pol = _scripted_policy(env, action, candidates, lookahead)
+    if action == "steer" and eps > 0.0:
+        raise ValueError("eps > 0 needs action='index' (the exploration draw is an index draw)")
+    m = _check_scenarios(scenarios, env.K)
+    n, T = int(n_episodes), int(trajectory_steps)
+    if v0 is not None and tuple(np.shape(v0)) != (n, 2):
+        raise ValueError(f"v0 must be [{n}, 2] (got {tuple(np.shape(v0))})")
+    import torch
+    a = _lib.UavEvalArgs()
+    if action == "index":
+        records, pos, act, keep = _prepare(env, a, n, T, m, scenarios, first, seed, max_steps, v0, max_workgroups, (), -1, torch.int8)
+    else:
+        records, pos, act, keep = _prepare(env, a, n, T, m, scenarios, first, seed, max_steps, v0, max_workgroups, (), float("nan"),
+                                           torch.float32)
+    a.eps = float(eps)
+    _lib.check(env.lib.uavenv_eval_episodes_scripted(env._h, C.byref(pol), C.byref(a), env._stream()), "uavenv_eval_episodes_scripted")
+    res = EvalResult(records, pos, act)
+    res._keep = keep
+    return res
+
+
+def scripted_act(env, actions_out, *, action: str = "index", candidates=None, lookahead: int = 8):
+    """The scripted baseline's act launch alone (uavenv_scripted_act): actions_out[i] = the action of agent i of env in its
+    current state -- a contiguous [N] int32 tensor for action = "index", float32 for "steer", on the env's device -- ready for
+    env.step(actions_out, ...), so scripted transitions can fill a replay ring.  The env is only read.  -> actions_out."""
+    pol = _scripted_policy(env, action, candidates, lookahead)
+    import torch
+    want = torch.int32 if action == "index" else torch.float32
+    if not isinstance(actions_out, torch.Tensor) or actions_out.dtype != want:
+        raise ValueError(f"actions_out must be a {want} tensor for action={action!r}")
+    if actions_out.numel() != env.N or not actions_out.is_contiguous() or actions_out.device != env.device:
+        raise ValueError("actions_out must be a contiguous [N] tensor on the env device")
+    _lib.check(env.lib.uavenv_scripted_act(env._h, C.byref(pol), actions_out.data_ptr(), env._stream()), "uavenv_scripted_act")
+    return actions_out
 
 
 def sac_noise(n: int, steps: int, seed: int, device="cuda:0"):

@@ -416,6 +416,45 @@ class PathPlan_City:
     def run_XML_scene(self):
         pass
 
+    def _evaluation_missions(self, n: int, seed: int, held_out: bool):
+        """The n missions evaluate_policy and evaluate_baseline fly, each repeated for every UAV slot with ONE initial heading
+        (evaluate.slot_scenarios: episode r * U + j = mission r as slot j): held-out rows planned now on a seed of their own, or the
+        first rows of the reset bank.  -> ((start_goal, sub_goals, n_sub) device tensors of n * U rows, v0 [n * U, 2])."""
+        from dqn_based_uav_3d_path_planer_amd import evaluate as _ev
+        if held_out:
+            scn = _ev.held_out_scenarios(self.backend, n, seed=0x7E57_0000 + int(seed))
+        else:
+            m = self.backend.bank_stats()[0]
+            sg, sub, ns = self.backend.bank_read(0, min(n, m))
+            rows = np.arange(n) % len(sg)
+            d = self.backend.device
+            scn = (torch.tensor(sg[rows], device=d), torch.tensor(sub[rows], device=d), torch.tensor(ns[rows], device=d))
+        return _ev.slot_scenarios(scn, self.num_UAV, float(self.backend.cfg.max_v), seed)
+
+    def evaluate_baseline(self, n_episodes: int = 1024, seed: int = 0, held_out: bool = True, max_steps: int = 0, lookahead: int = 8,
+                          candidates: int = 9):
+        """The scripted baseline (sub-goal pursuit with look-ahead, evaluate.evaluate_scripted_policy: no learning) on the missions
+        and initial headings evaluate_policy(seed=...) flies: one summary dict per slot, all slots in ONE launch -- the yardstick
+        for evaluate_policy's numbers.  With DQN-family trainers in the slots it chooses among the env's discrete actions (what
+        they choose among; `candidates` is not used), with fused SAC trainers among `candidates` steers in [-1, 1].  `lookahead`:
+        the steps a candidate is probed ahead (0: pure pursuit).  The env, its agents and the replay are left as they were."""
+        from dqn_based_uav_3d_path_planer_amd import evaluate as _ev
+        from dqn_based_uav_3d_path_planer_amd.sac import FusedSACLearner
+        if not hasattr(self.backend, "rrt_plan"):
+            raise RuntimeError("evaluate_baseline needs the GPU backend")
+        n, U = int(n_episodes), self.num_UAV
+        if n <= 0:
+            raise ValueError(f"n_episodes must be positive (got {n_episodes!r})")
+        sac = [isinstance(getattr(u.Trainer, "learner", None), FusedSACLearner) for u in self.Agents]
+        if any(sac) and not all(sac):
+            raise RuntimeError("evaluate_baseline: the slots mix fused SAC trainers with others")
+        kind = dict(action="steer", candidates=candidates) if all(sac) else dict(action="index", candidates=None)
+        _ev._scripted_policy(self.backend, lookahead=lookahead, **kind)          # (refuse bad arguments before the planner runs)
+        scn_u, v0 = self._evaluation_missions(n, seed, held_out)
+        rec = _ev.evaluate_scripted_policy(self.backend, n * U, scenarios=scn_u, v0=v0, seed=int(seed), max_steps=int(max_steps),
+                                           lookahead=lookahead, **kind).host_records()
+        return [_ev.summarize(rec[j::U]) for j in range(U)]
+
     def evaluate_policy(self, n_episodes: int = 1024, seed: int = 0, held_out: bool = True, max_steps: int = 0, mode: str = "mean"):
         """Evaluation of every UAV slot's trainer: one summary dict per slot (dqn_based_uav_3d_path_planer_amd/evaluate.py).
         DQN-family trainers act greedily (Trainer/DuelingDQN_Trainer.py:90, Is_Train == 0); fused SAC trainers fly their actor
@@ -441,15 +480,7 @@ class PathPlan_City:
             for u, learner in zip(self.Agents, learners):
                 if getattr(learner, "net", None) is None:
                     raise RuntimeError(f"evaluate_policy: {u.name}'s trainer has no fused DQN-family or fused SAC learner")
-        if held_out:
-            scn = _ev.held_out_scenarios(self.backend, n, seed=0x7E57_0000 + int(seed))
-        else:
-            m = self.backend.bank_stats()[0]
-            sg, sub, ns = self.backend.bank_read(0, min(n, m))
-            rows = np.arange(n) % len(sg)
-            d = self.backend.device
-            scn = (torch.tensor(sg[rows], device=d), torch.tensor(sub[rows], device=d), torch.tensor(ns[rows], device=d))
-        scn_u, v0 = _ev.slot_scenarios(scn, U, float(self.backend.cfg.max_v), seed)
+        scn_u, v0 = self._evaluation_missions(n, seed, held_out)
         # episode r * U + j = mission r as slot j
         if all(sac):                                   # actor j flies the episodes = j (mod U), nothing else
             rec = _ev.evaluate_sac_policy(self.backend, learners, n * U, scenarios=scn_u, v0=v0, seed=int(seed), mode=mode,

@@ -615,6 +615,45 @@ int uavenv_eval_episodes_sac(UavEnv *env, const UavSacEvalArgs *args, void *stre
  * UAVENV_EINVAL for n <= 0, steps <= 0, n * steps >= 2^31 or a NULL / misaligned (4 bytes) pointer. */
 int uavenv_eval_noise_fill(uint64_t seed, int32_t n, int32_t steps, float *out_dev, void *stream);
 
+/* ---- a scripted baseline policy: sub-goal pursuit with look-ahead (no learning; the yardstick the learned policies are held to) ------
+ * The policy reads an agent's position, current sub-goal (with APF: its own shifted list head), cached heading
+ * (calculate_angle(0, V_vector)), the number of sub-goals left and the world.  Candidate steers k = 0 .. C - 1:
+ *   UAVENV_ACT_INDEX_I32  C = the env's n_actions (2..32), steer_k = -1 + 2k / (C - 1) as uavenv_step decodes index k; candidates = 0;
+ *   UAVENV_ACT_STEER_F32  C = candidates (odd, 3..17), steer_k = (double)(float)(-1 + 2k / (C - 1)), as uavenv_step reads an f32 steer.
+ * Rule: no sub-goal left -> candidate C / 2.  Otherwise err = calculate_angle(sub0 - pos) - heading wrapped into (-pi, pi],
+ * s* = clamp(err / Steering_angle, -1, 1), cost_k = |steer_k - s*|.  Candidate k is blocked where Threaten_rate(pos + t V_k) = 1 for
+ * some t = 1 .. lookahead, V_k being the V_vector update_PathPlan sets for steer_k (UAV.py:411-417, Calc_V's clamp included: the t = 1
+ * point is bit for bit where the step moves to); lookahead = 0 blocks nothing.  The policy takes the unblocked candidate of least
+ * cost, the lower k on equal cost; with every candidate blocked, the least cost among the candidates whose next point (t = 1) is
+ * free; with none of those either, the least cost overall.  So with lookahead >= 1 a step takes the collision branch
+ * (UAV.py:425-428) only when every candidate's next point was blocked.
+ *
+ * uavenv_scripted_act: the act launch alone, one lane per agent of the env: actions_out[i] (dev, [N], 4-byte aligned) = the int32
+ * index or the f32 steer of agent i's candidate, the middle candidate C / 2 for a done agent -- what uavenv_step takes as
+ * UAVENV_ACT_INDEX_I32 / UAVENV_ACT_STEER_F32.  The env is only read.
+ *
+ * uavenv_eval_episodes_scripted: uavenv_eval_episodes with this policy in the net's place, for APF and non-APF envs, in one launch
+ * that stages nothing but the world.  Episodes, scenario rows, the reset, v0 / the heading draw, UavEvalArgs, UavEvalRecord, the end of
+ * an episode, truncation, invalid rows, max_workgroups and what is left untouched on the env are uavenv_eval_episodes'; slot
+ * j = e mod uav_per_env; with APF on the lanes fly on the env-owned workspace of uavenv_eval_episodes_sac / _slots.  Index kind:
+ * args->eps > 0 replaces the choice by uavenv_eval_episodes' exploration draw (Philox (seed; e, step, 0, 0xe75f)), so eps = 1 is
+ * that entry's random policy bit for bit; traj_act is int8 [n][traj_steps].  Steer kind: traj_act points to float [n][traj_steps]
+ * (4-byte aligned), the f32 steer of every step.  A record does not depend on the grid.
+ * UAVENV_EINVAL, with nothing enqueued or allocated, for: an action_kind other than the two; candidates even, outside 3..17 or (index
+ * kind) non-zero; lookahead outside 0..16; the index kind on an env with more than 32 actions; eps > 0 with the steer kind; no world;
+ * and every argument uavenv_eval_episodes refuses. */
+#define UAVENV_SCRIPTED_MAX_LOOKAHEAD 16
+#define UAVENV_SCRIPTED_MAX_STEER_CANDIDATES 17
+#define UAVENV_SCRIPTED_MAX_INDEX_ACTIONS 32
+typedef struct UavScriptedPolicy {
+    int32_t action_kind;            /* UAVENV_ACT_INDEX_I32 | UAVENV_ACT_STEER_F32 */
+    int32_t candidates;             /* steer kind: C, odd, 3..17; index kind: 0 (C = the env's n_actions) */
+    int32_t lookahead;              /* H, 0..16 */
+    int32_t reserved0;
+} UavScriptedPolicy;
+int uavenv_scripted_act(UavEnv *env, const UavScriptedPolicy *policy, void *actions_out, void *stream);
+int uavenv_eval_episodes_scripted(UavEnv *env, const UavScriptedPolicy *policy, const UavEvalArgs *args, void *stream);
+
 /* ---- multi-GPU: one-shot all-reduce of the gradient bucket over peer-mapped HBM (csrc/p2p.hip) ------------------- */
 /* One UavP2P per rank (= per GPU / process).  create -> every rank publishes its UAVENV_P2P_HANDLE_BYTES handle
  * (uavenv_p2p_handle) -> the `world` handles, in rank order, go to uavenv_p2p_connect on every rank.  Then, per update,

@@ -2,8 +2,9 @@
 packed replay ring), with a greedy evaluation of held-out city26 episodes (uavenv_eval_episodes) every --every passes.
 
 The settings (envs, learner batch, replay capacity, trainer, training epsilon, reset bank) come from bench.py's own defaults
-(bench.parse()), so this measures the loop the benchmark times.  Baselines at pass 0: the untrained net (greedy) and eps = 1 (the
-uniform random policy).  Held-out rows are planned on a seed the training bank never uses.  Output: one JSON document.
+(bench.parse()), so this measures the loop the benchmark times.  Baselines at pass 0: the untrained net (greedy), eps = 1 (the
+uniform random policy) and the scripted baseline (sub-goal pursuit among the same three actions, no learning:
+uavenv_eval_episodes_scripted) with look-ahead 0 and 8.  Held-out rows are planned on a seed the training bank never uses.  Output: one JSON document.
     python scripts/learning_curve.py [--passes 1000000] [--every 50000] [--episodes 16384] [--out profiles/learning_curve_configs1.json]
 
 --config 2: BASELINE configs[2] as `bench.py --config 3` builds it (65 536 envs, dueling + DDQN, f16 observation rows, the f16-MFMA
@@ -16,7 +17,7 @@ velocities of default_rng(42), one fused SAC learner per slot, SACHotLoop), with
 launch (uavenv_eval_episodes_sac) every --every passes, in both modes ("mean": noise 0; "sample": as get_action flies).  Every
 slot flies the same --episodes missions from the same headings (evaluate.slot_scenarios).  Baselines at pass 0: the untrained
 actors in both modes, and a uniform steer ~ U[-1, 1] per step flown through uavenv_step on a scratch env (the SAC kernel takes no
-caller-supplied actions).
+caller-supplied actions), and the scripted baseline among 9 steers with look-ahead 0 and 8.
     python scripts/learning_curve.py --config 3 [--passes 40000] [--every 4000] [--episodes 4096] [--out profiles/learning_curve_configs3.json]
 """
 from __future__ import annotations
@@ -56,6 +57,17 @@ def evaluation(env, learner, scn, n, max_steps, eps=0.0):
     s = ev.evaluate_policy(env, learner, n, scenarios=scn, seed=11, eps=eps, max_steps=max_steps).summary()
     return {k: s[k] for k in ("episodes", "success", "lose", "truncated", "success_rate", "lose_rate", "mean_return",
                               "mean_steps", "mean_path_len", "mean_subgoals", "mean_collisions", "average_score")}
+
+
+def scripted_baselines(env, scn, n, max_steps, U=1, v0=None, **kind):
+    """The scripted baseline (evaluate.evaluate_scripted_policy: sub-goal pursuit, no learning) on the same held-out missions, as
+    pure pursuit (look-ahead 0) and with look-ahead 8 -> {"scripted_h0": ..., "scripted_h8": ...}; U > 1: one summary per slot."""
+    out = {}
+    for H in (0, 8):
+        rec = ev.evaluate_scripted_policy(env, n, scenarios=scn, v0=v0, seed=11, max_steps=max_steps, lookahead=H, **kind).host_records()
+        summ = [{k: s[k] for k in KEYS} for s in (ev.summarize(rec[j::U]) for j in range(U))]
+        out["scripted_h%d" % H] = summ if U > 1 else summ[0]
+    return out
 
 
 KEYS = ("episodes", "success", "lose", "truncated", "success_rate", "lose_rate", "mean_return", "mean_steps", "mean_path_len",
@@ -158,6 +170,7 @@ def main_config3(args):
            "baselines": {"untrained_mean": evaluation("mean"), "untrained_sample": evaluation("sample"),
                          "uniform_steer": uniform_steer_baseline(vel, scn_u, v0, U, args.max_steps, seed=11)},
            "curve": []}
+    out["baselines"].update(scripted_baselines(env, scn_u, args.episodes * U, args.max_steps, U=U, v0=v0, action="steer", candidates=9))
     print(json.dumps({"baselines": out["baselines"]}), flush=True)
     done, t0 = 0, time.perf_counter()
     while done < args.passes:
@@ -220,6 +233,7 @@ def main():
            "baselines": {"untrained_greedy": evaluation(env, learner, scn, args.episodes, args.max_steps),
                          "random_eps1": evaluation(env, learner, scn, args.episodes, args.max_steps, eps=1.0)},
            "curve": []}
+    out["baselines"].update(scripted_baselines(env, scn, args.episodes, args.max_steps, action="index"))
     print(json.dumps({"baselines": out["baselines"]}), flush=True)
     done, t0 = 0, time.perf_counter()
     while done < args.passes:

@@ -29,6 +29,13 @@ SKIP_DONE; on the f16 env, where uavenv_step_policy takes the shape (at most 65 
 per step is timed as well.  Launches only, device events, a warm-up of every form, then the forms alternating in the same process,
 median of the repeats; every record checked equal before a time is taken.
     python scripts/time_eval.py --f16 [--reps 5] [--max-steps 600] [--out profiles/eval_f16_times.json]
+
+--scripted: the scripted baseline (uavenv_eval_episodes_scripted; the index kind on the env's 3 actions, look-ahead 8, U = 4), APF off
+and on, against set_state + per step uavenv_scripted_act + uavenv_step with SKIP_DONE and no observation (nothing reads one) in its
+default form (k_apf_adjust + k_step on the APF env).  Launches only, device events, a warm-up of both forms, then the two forms
+alternating in the same process, median of the repeats; every record checked equal before a time is taken.  --once N: no timing, one
+launch per APF setting at N episodes (for a kernel-trace run).
+    python scripts/time_eval.py --scripted [--reps 5] [--max-steps 600] [--lookahead 8] [--out profiles/eval_scripted_times.json]
 """
 from __future__ import annotations
 
@@ -538,6 +545,108 @@ def main_slots(args):
         json.dump(out, f, indent=1)
 
 
+class ScriptedComposition(SacComposition):
+    """SacComposition with the scripted baseline's act launch in the actors' place; the step launch writes no observation."""
+
+    def __init__(self, scn, n, v0, apf, max_steps, lookahead, U=4):
+        self.n, self.U, self.max_steps = n, U, max_steps
+        sg, sub, ns = (x.cpu().numpy() for x in scn)
+        rows = np.arange(n) % len(sg)
+        self.env = make_city26_env(n // U, obs_dtype="packed", uav_per_env=U, apf_enabled=apf)
+        if apf:
+            self.env.set_buildings(self.env.buildings, velocities=apf_velocities(len(self.env.buildings)))
+        self.kin = np.concatenate([sg[rows, :3], v0, sg[rows, 3:]], 1)
+        self.nsub = ns[rows]
+        self.sub = sub[rows]
+        d = self.env.device
+        self.act = torch.zeros(n, dtype=torch.int32, device=d)
+        self.r64 = torch.zeros(n, dtype=torch.float64, device=d)
+        self.en = torch.zeros(n, dtype=torch.float64, device=d)
+        self.info = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.adone = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.valid = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.pol = ev._scripted_policy(self.env, "index", None, lookahead)
+
+    def reset(self):
+        self.env.set_state(0, self.kin, np.zeros(self.n, np.int32), self.nsub, self.sub, alias=(self.nsub >= 2).astype(np.int32))
+
+    def step(self, t):
+        e = self.env
+        _lib.check(e.lib.uavenv_scripted_act(e._h, C.byref(self.pol), self.act.data_ptr(), e._stream()), "uavenv_scripted_act")
+        _lib.check(e.lib.uavenv_step(e._h, self.act.data_ptr(), _lib.ACT_INDEX_I32, None, self.r64.data_ptr(), None,
+                                     None, self.adone.data_ptr(), self.info.data_ptr(), self.valid.data_ptr(),
+                                     self.en.data_ptr(), None, _lib.STEP_SKIP_DONE | _lib.STEP_NO_OBS, e._stream()), "uavenv_step")
+
+
+def scripted_v0(n):
+    t = np.random.default_rng(n).uniform(0, 2 * np.pi, n)
+    return np.stack([np.cos(t), np.sin(t)], 1)
+
+
+def main_scripted(args):
+    torch.cuda.set_device(0)
+    probe = make_city26_env(64, obs_dtype="packed")
+    scn = ev.held_out_scenarios(probe, 16384, seed=0xE7A1)
+    probe.close()
+    U, H = 4, args.lookahead
+    if args.once > 0:                                # one launch per APF setting (for a kernel-trace run)
+        for apf in (0, 1):
+            env = make_city26_env(64, obs_dtype="packed", uav_per_env=U, apf_enabled=apf)
+            if apf:
+                env.set_buildings(env.buildings, velocities=apf_velocities(len(env.buildings)))
+            s = ev.evaluate_scripted_policy(env, args.once, scenarios=scn, v0=scripted_v0(args.once), lookahead=H,
+                                            max_steps=args.max_steps).summary()
+            print(json.dumps({"apf": apf, "episodes": args.once, "mean_steps": s["mean_steps"]}), flush=True)
+            env.close()
+        return
+    out = {"what": "the scripted baseline (index kind, 3 actions, look-ahead %d, U = 4) on held-out city26 episodes in one launch "
+                   "(uavenv_eval_episodes_scripted) against uavenv_scripted_act + uavenv_step without observations (k_apf_adjust + k_step "
+                   "with APF on); launches only, device events, a warm-up, the two forms alternating, median of %d" % (H, args.reps),
+           "max_steps": args.max_steps, "lookahead": H, "sizes": []}
+    for apf in (0, 1):
+        for n in (int(x) for x in args.sizes.split(",")):
+            v0 = scripted_v0(n)
+            comp = ScriptedComposition(scn, n, v0, apf, args.max_steps, H, U)
+            ref, n_steps = comp.records()
+            kw = dict(scenarios=scn, v0=v0, lookahead=H, max_steps=args.max_steps)
+            res = ev.evaluate_scripted_policy(comp.env, n, **kw)
+            rec = res.host_records()
+            ok = (np.array_equal(rec["ret"], ref["ret"]) and np.array_equal(rec["energy"], ref["energy"]) and
+                  np.array_equal(rec["steps"], ref["steps"]) and np.array_equal(rec["outcome"], ref["outcome"]))
+            if not ok:
+                raise SystemExit(f"apf {apf}, n = {n}: the kernel's records differ from the composition's; no time reported")
+            agent_steps = int(rec["steps"].sum())
+
+            def timed_eval():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                ev.evaluate_scripted_policy(comp.env, n, **kw)
+                b.record()
+                b.synchronize()
+                return a.elapsed_time(b)
+
+            timed_eval()
+            comp.timed(min(n_steps, 32))
+            t_eval, t_comp = [], []
+            for _ in range(args.reps):               # the two forms alternating
+                t_eval.append(timed_eval())
+                t_comp.append(comp.timed(n_steps))
+            me, mc = float(np.median(t_eval)), float(np.median(t_comp))
+            row = {"apf": apf, "episodes": n, "agent_steps": agent_steps, "steps_longest": n_steps, "records_equal": True,
+                   "eval_ms": me, "eval_ms_all": t_eval, "comp_ms": mc, "comp_ms_all": t_comp,
+                   "comp_form": "scripted_act + " + ("apf_adjust + step" if apf else "step") + " (no observation)",
+                   "eval_agent_steps_per_s": agent_steps / (me * 1e-3), "comp_agent_steps_per_s": agent_steps / (mc * 1e-3),
+                   "eval_us_per_episode": me * 1e3 / n, "comp_us_per_episode": mc * 1e3 / n, "speedup": mc / me,
+                   "summary": res.summary()}
+            print(json.dumps({k: v for k, v in row.items() if not k.endswith("_all") and k != "summary"}), flush=True)
+            out["sizes"].append(row)
+            comp.env.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main_slots_once(args):
     """One uavenv_eval_episodes_slots launch per APF setting at `--once` episodes per net (for a kernel-trace run)."""
     torch.cuda.set_device(0)
@@ -570,8 +679,13 @@ def main():
     ap.add_argument("--max-steps", type=int, default=600, help="--sac / --slots / --f16: truncate episodes (0: natural ends)")
     ap.add_argument("--slots", action="store_true", help="time uavenv_eval_episodes_slots (four DQN nets, APF off and on) instead")
     ap.add_argument("--f16", action="store_true", help="time uavenv_eval_episodes_f16 (an f16-MFMA net on f16 and packed rows) instead")
-    ap.add_argument("--once", type=int, default=0, help="--slots: no timing, one launch per APF setting at this many episodes per net")
+    ap.add_argument("--once", type=int, default=0, help="--slots / --scripted: no timing, one launch per APF setting at this many episodes (per net)")
+    ap.add_argument("--scripted", action="store_true", help="time uavenv_eval_episodes_scripted (the scripted baseline, APF off and on) instead")
+    ap.add_argument("--lookahead", type=int, default=8, help="--scripted: the policy's look-ahead")
     args = ap.parse_args()
+    if args.scripted:
+        args.out = args.out or "profiles/eval_scripted_times.json"
+        return main_scripted(args)
     if args.f16:
         args.out = args.out or "profiles/eval_f16_times.json"
         return main_f16(args)
