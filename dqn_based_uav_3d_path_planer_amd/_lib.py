@@ -358,6 +358,7 @@ def load() -> C.CDLL:
                "uavenv_sac_critic_adam_multi", "uavenv_sac_actor_adam_multi"):       # (called from csrc/loop.hip and by the kernel tests)
         getattr(lib, _n).restype = C.c_int
     # arrays of n slots: nets / batches / Adam headers as ctypes arrays of the structures, `float *const *` as arrays of c_void_p
+    lib.uavenv_sac_act_multi.argtypes = [vp, vp, vp, i32, i32, vp, f32, vp, vp, i32, vp]
     lib.uavenv_sac_critic_grad_multi.argtypes = [vp, vp, i32, f32, f32, vp, vp]
     lib.uavenv_sac_actor_grad_multi.argtypes = [vp, vp, i32, f32, vp, vp]
     lib.uavenv_sac_critic_adam_multi.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp]

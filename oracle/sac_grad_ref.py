@@ -451,3 +451,24 @@ def assert_stress(hd: dict):
 def actor_forward(X, actor, eps, mut=None) -> dict:
     """The actor's forward (head included) on rows X with draws eps: see actor_head_f64; plus o, m_abs, s_abs, lp_abs."""
     return _actor_fwd(np.asarray(X, dtype=np.float64), actor, eps, mut)
+
+
+def act_bar(hd: dict, tau_td: float, u: float):
+    """The acting bar on |action - act| per (row, action dimension), hd from actor_forward: the head's pre-activations within tau_td
+    of their |.|-forward, carried to the action to first order, plus 8 u for the four tanhf / expf / log1pf calls and the product
+    sd eps on values of size <= 1 + |eps| (derived in tests/test_sac_grad_kernels_gpu.py::test_act_on_the_stress_actor)."""
+    one_act, one_mu = 1 - hd["act"] ** 2, 1 - hd["mu"] ** 2
+    dsd = (1 - hd["sd"] ** 2) * hd["sig"]
+    return tau_td * one_act * (one_mu * hd["m_abs"] + np.abs(hd["eps"]) * dsd * hd["s_abs"]) + 8 * u * (1 + np.abs(hd["eps"]))
+
+
+def act_launch_map(n_slots: int, count: int, budget: int = 512) -> dict:
+    """How uavenv_sac_act_multi spreads one slot's `count` agents: max(1, budget / n_slots) workgroups per slot (budget =
+    UAVENV_SAC_ACT_WGS, 512 unless set), 64 agents per tile, tile t to workgroup t mod gx on trip t div gx.
+    -> gx, tiles, trips, trip [tiles], wg [tiles], last (rows of the last tile), late (workgroups that take the last trip)."""
+    gx = max(1, budget // n_slots)
+    tiles = (count + TILE - 1) // TILE
+    t = np.arange(tiles)
+    trip, wg = t // gx, t % gx
+    return dict(gx=gx, tiles=tiles, trips=int(trip.max()) + 1, trip=trip, wg=wg, last=count - (tiles - 1) * TILE,
+                late=int((trip == trip.max()).sum()))

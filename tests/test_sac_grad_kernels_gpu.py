@@ -49,7 +49,8 @@ Per case:
  (g) *_grad_multi with 4 slots of different batch sizes and pins (grids 1, 13, 8, 1: three slots take the early return), different
      nets per slot: bit-identical to the single-slot launches, rows beyond a slot's grid untouched; *_adam_multi bit-identical to
      the single calls.
- (h) k_sac_act on the stress actor (ragged count, strided rows) against actor_head_f64.
+ (h) k_sac_act on the stress actor (ragged count, strided rows) against actor_head_f64; its bar is oracle.sac_grad_ref.act_bar, which
+     tests/test_sac_act_kernels_gpu.py holds the batched launch to at every slot count and tile trip.
  (i) UAVENV_SAC_FUSED_TD=1 in-process against f64; UAVENV_SAC_WGS in a fresh child.
 Ambiguity cap, asserted on the host before the launch (the batch's seed is the first that meets it): ReLU pre-activations within
 relu_eps of zero at most 1 % of (sample, unit) pairs, |Q1 - Q2| within tie_eps at most 1 % of (sample, output column) pairs.  (Not "1 %
@@ -72,8 +73,8 @@ import numpy as np
 import pytest
 import torch
 
-from oracle.sac_grad_ref import (MUTS, PA, PC, actor_forward, assert_stress, sac_actor_bucket_f64, sac_adam_f64, sac_critic_bucket_f64,
-                                 sample_contribution, stress_actor)
+from oracle.sac_grad_ref import (MUTS, PA, PC, act_bar, actor_forward, assert_stress, sac_actor_bucket_f64, sac_adam_f64,
+                                 sac_critic_bucket_f64, sample_contribution, stress_actor)
 
 pytestmark = pytest.mark.gpu
 
@@ -796,9 +797,7 @@ def test_act_on_the_stress_actor():
         if count > 1000:
             assert_stress(hd)
         got = np.stack([a0.cpu().numpy()[rows], a1.cpu().numpy()[rows]], 1).astype(np.float64)
-        one_act, one_mu = 1 - hd["act"] ** 2, 1 - hd["mu"] ** 2
-        dsd = (1 - hd["sd"] ** 2) * hd["sig"]
-        bar = BARS["tau_td"] * one_act * (one_mu * hd["m_abs"] + np.abs(hd["eps"]) * dsd * hd["s_abs"]) + 8 * U * (1 + np.abs(hd["eps"]))
+        bar = act_bar(hd, BARS["tau_td"], U)
         assert np.isfinite(got).all()
         worst = max(worst, float((np.abs(got - hd["act"]) / bar).max()))
         un = np.ones(n_rows, dtype=bool)
