@@ -51,6 +51,37 @@ class _RingMemoryView:
                     dones=b["dones"], valid=b["valid"])
 
 
+def count_chunk(stats, moved=None):
+    """The accounting of one chunk of passes the fused episode loops read back (PathPlan_City._read_chunk): row i of `stats` is
+    pass i -- column 0 the agents it moved, columns 1..3 the normal / success / lose infos among them, columns 4.. (when present)
+    the moved agents of each UAV slot.  The first pass that moved nobody found every agent finished: the episode ended before it,
+    and neither it nor the passes behind it count.  `moved` replaces column 0 in that test (several ranks: the sum over the ranks,
+    so that they leave the episode together; the counts stay this rank's own).
+    -> (passes counted, ended, {"normal", "success", "lose": increments}, [increment of every UAV slot])."""
+    stats = np.asarray(stats)
+    idle = np.flatnonzero(np.asarray(stats[:, 0] if moved is None else moved) == 0)
+    n = int(idle[0]) if len(idle) else len(stats)
+    sums = stats[:n, 1:].sum(axis=0)
+    return n, n < len(stats), {nm: int(sums[c]) for c, nm in enumerate(("normal", "success", "lose"))}, [int(x) for x in sums[3:]]
+
+
+def assemble_actions(chosen, act_nums):
+    """What every UAV slot's trainer chose for all envs -> the [num_envs, num_UAV] action tensor backend.step takes: int32 indices
+    when every slot chose an index; else float32 steers -- SAC's [n, action_dim], of which only [:, 0] steers (UAV.py:414), and
+    an index c of a slot with act_nums[j] actions on the documented table -1 + 2 c / (act_num - 1)."""
+    continuous = any(c.dim() == 2 for c in chosen)
+    actions = torch.zeros((chosen[0].shape[0], len(chosen)), dtype=torch.float32 if continuous else torch.int32,
+                          device=chosen[0].device)
+    for j, c in enumerate(chosen):
+        if c.dim() == 2:
+            actions[:, j] = c[:, 0].float()
+        elif continuous:
+            actions[:, j] = -1.0 + 2.0 * c.float() / (act_nums[j] - 1)
+        else:
+            actions[:, j] = c.to(torch.int32)
+    return actions
+
+
 class PathPlan_City:
     def __init__(self, param: dict) -> None:
         # ---- BaseEnv.__init__ (BaseClass/BaseEnv.py:17-34)
@@ -609,6 +640,92 @@ class PathPlan_City:
         self._obs_raw = ring.obs[ring.head]
         self._invalidate()
 
+    # ---- the frame the three fused episode loops share: each loop below holds only what is particular to its path -----------
+    # What stays in each of them is the accounting of the surplus passes (enqueued behind the end of the episode), side by side:
+    #                 single net (HotLoop)           one DQN net per slot              one SAC learner per slot
+    #   undone        epoch, by min(surplus, taken)  every learner's epoch, same min   epoch and adam_steps; nothing with several ranks
+    #   PER beta      recomputed when undo > 0       recomputed whenever trees are on  recomputed when surplus > 0, one rank
+    #   Philox        _hot_counter, when surplus > 0 _slots_counter, always            _sac_counter -= surplus, one rank
+    #   loop object   closed when surplus > 0        closed when surplus > 0           closed when surplus > 0
+    #   n_entries     ring.filled * backend.N        ring.filled * num_envs            ring.filled * num_envs
+    def _begin_fused_episode(self, eps_rate) -> int:
+        """Open an episode on the packed ring: UAV.reset everywhere, straight into the ring's current frame (the replay stays).
+        -> k, the passes enqueued between two looks at the device."""
+        self.Reset_Result(eps_rate)
+        ring = self._ring
+        self._episode += 1
+        self._refresh_bank()
+        self.backend.reset(self.seed + self._episode, obs=ring.obs[ring.head])
+        self._obs_raw = ring.obs[ring.head]
+        self._invalidate()
+        self._paths, self._path_done = [[] for _ in range(self.num_UAV)], [False] * self.num_UAV
+        return 1 if self.record_path else min(self.done_check, ring.frames - 2)
+
+    def _read_chunk(self, t0: int, k: int, per_slot: bool = False) -> np.ndarray:
+        """What the k passes that began at frame t0 did, in ONE device-to-host transfer: per pass the agents it moved and the
+        normal / success / lose infos among them; with per_slot also the moved agents of every UAV slot (count_chunk's columns)."""
+        ring = self._ring
+        fr = (t0 + torch.arange(k, device=self.backend.device)) % ring.frames
+        v = ring.valid[fr].bool()                                                    # [k, N] agents moved by each pass
+        inf = self._info[fr]
+        stats = torch.stack([v.sum(1)] + [((inf == c) & v).sum(1) for c in range(3)], 1)
+        if per_slot:
+            stats = torch.cat([stats, v.view(k, -1, self.num_UAV).sum(1)], 1)
+        return stats.cpu().numpy()                                                   # the one sync
+
+    def _tally_chunk(self, stats, moved=None):
+        """count_chunk applied to the episode's result.  -> (passes counted, ended, [moved agents of every UAV slot])."""
+        n, ended, counts, per_slot = count_chunk(stats, moved)
+        for name, c in counts.items():
+            self.result[name] += c
+        return n, ended, per_slot
+
+    def _after_chunk(self):
+        """The UAV views read the frame the ring now stands at."""
+        self._obs_raw = self._ring.obs[self._ring.head]
+        self._invalidate()
+        self._record_paths(range(self.num_UAV))
+
+    def _trainer_item(self, uav, saved_on):
+        """One UAV's entry for Train_statistics after an episode of a fused loop; save() as _learn does, once per save_loop
+        updates.  `saved_on` keeps the mark of the last save: the env on the single-net path, the trainer where each slot has its own."""
+        tr = uav.Trainer
+        tr.loss = tr.learner.loss
+        item = {"loss": tr.learner.loss, "sum_epoch": tr.epoch, "score": uav.score, "average_score": uav.score,
+                "step": uav.Step, "energy_cost": uav.energy_cost_total, "task_collect": uav.task_collect,
+                "Energy_Efficent": uav.task_collect / (uav.energy_cost_total + 0.001), "UE_waiting_time": 0}
+        if tr.Is_Train and tr.epoch // tr.save_loop != getattr(saved_on, "_saved_at", 0):
+            saved_on._saved_at = tr.epoch // tr.save_loop
+            tr.save()
+        return item
+
+    def _end_episode(self, train_info, n_steps=None, record=None):
+        """:466-478, the end of every episode loop: statistics, epoch += 1, record_list (of `record`: every agent unless given),
+        the federated merge."""
+        self.Train_statistics(train_info)
+        if n_steps is not None:
+            self.steps_last_episode = n_steps
+        self.epoch += 1
+        if self.epoch % self.print_loop == 0:
+            for uav in (self.Agents if record is None else record):
+                uav.record_list()
+        self._federated_merge()
+        return self.result
+
+    def _step_chosen(self, chosen):
+        """One time step of the general and on-policy loops: every slot's chosen actions -> backend.step (done agents wait,
+        :365-366 / :388-389) and the info counts of the agents it moved (Run_statistics, :395).  -> (out, valid [num_envs, num_UAV])."""
+        actions = assemble_actions(chosen, [getattr(u.Trainer, "act_num", None) for u in self.Agents])
+        out = self.backend.step(actions.reshape(-1).contiguous(), skip_done=True)
+        self._obs = out.obs
+        self._invalidate()
+        self._record_paths(range(self.num_UAV))
+        info = out.info.view(self.num_envs, self.num_UAV)
+        valid = out.valid.view(self.num_envs, self.num_UAV).bool()
+        for c, name in enumerate(("normal", "success", "lose")):
+            self.result[name] += int(((info == c) & valid).sum().item())
+        return out, valid
+
     def _run_eposide_fused(self, eps_rate):
         """run_eposide on the fused path: HotLoop enqueues done_check steps of act -> step (+ replay write) -> sample ->
         learn at a time; the host then reads, in one transfer, how many agents each of those steps still moved and the
@@ -617,15 +734,9 @@ class PathPlan_City:
         learner does take that many extra replay updates -- the one deviation from the reference's loop, which breaks
         right after the update of the last moving step, PathPlan_City.py:456-459)."""
         from dqn_based_uav_3d_path_planer_amd.loop import HotLoop
-        self.Reset_Result(eps_rate)
         uav = self.Agents[0]
         tr, ring = uav.Trainer, self._ring
-        self._episode += 1
-        self._refresh_bank()
-        self.backend.reset(self.seed + self._episode, obs=ring.obs[ring.head])      # UAV.reset everywhere; the replay stays
-        self._obs_raw = ring.obs[ring.head]
-        self._invalidate()
-        self._paths, self._path_done = [[] for _ in range(self.num_UAV)], [False] * self.num_UAV
+        k = self._begin_fused_episode(eps_rate)
         batch_now = tr.Batch_Size if tr.Is_Train else 0
         if self._hot is not None and not self._hot.in_sync(batch_now):
             self._hot_counter = self._hot.counter   # the Philox stream goes on where the old loop stopped
@@ -636,9 +747,7 @@ class PathPlan_City:
                                 learn_start=tr.Batch_Size + 1, auto_reset=False, skip_done=True, info=self._info,
                                 per=getattr(self, "_per", None), counter=getattr(self, "_hot_counter", 0), gate_updates=True)
         self._hot.set_eps(eps_rate if tr.Is_Train else 0.0)
-        k = 1 if self.record_path else min(self.done_check, ring.frames - 2)
         n_steps, ended = 0, False
-        dev = self.backend.device
         epoch0, passes = tr.learner.epoch, 0
         per = getattr(self, "_per", None)
         self.hot_loop_with_per = self._hot._per is not None
@@ -647,52 +756,27 @@ class PathPlan_City:
             t0 = ring.head
             self._hot.run(k)
             passes += k
-            fr = (t0 + torch.arange(k, device=dev)) % ring.frames
-            v = ring.valid[fr].bool()                                                # [k, N] agents moved by each step
-            inf = self._info[fr]
-            stats = torch.stack([v.sum(1)] + [((inf == c) & v).sum(1) for c in range(3)], 1).cpu().numpy()   # one sync
-            for i in range(k):
-                if stats[i, 0] == 0:                                                 # nobody moved: finished before this step
-                    ended = True
-                    break
-                n_steps += 1
-                self.result["normal"] += int(stats[i, 1])
-                self.result["success"] += int(stats[i, 2])
-                self.result["lose"] += int(stats[i, 3])
-            self._obs_raw = ring.obs[ring.head]
-            self._invalidate()
-            if self.record_path:
-                self._record_paths(range(self.num_UAV))
+            n, ended, _ = self._tally_chunk(self._read_chunk(t0, k))
+            n_steps += n
+            self._after_chunk()
         # The passes enqueued behind the last moving step changed nothing on the device (HotLoop(gate_updates): the Adam launch and
         # batch_update check the word the step kernel stamps) -- the counters follow: the learner has taken exactly one update per
         # moving step, as the reference's loop, which leaves right after the last one (Envs/PathPlan_City.py:456-459)
-        undo = min(passes - n_steps, tr.learner.epoch - epoch0)
-        if undo > 0:
+        surplus = passes - n_steps
+        undo = min(surplus, tr.learner.epoch - epoch0)
+        if undo > 0:                     # (beta only then: with nothing undone the loop's own running beta stands as it is)
             tr.learner.epoch -= undo
             if per is not None:
                 per.beta = min(1.0, beta0 + (tr.learner.epoch - epoch0) * per.beta_inc)
-        self.surplus_passes_last_episode = passes - n_steps
-        if passes > n_steps:             # ... and neither the replay cursor nor the Philox counter remembers them
-            self._hot_counter = self._hot.counter - (passes - n_steps)
+        self.surplus_passes_last_episode = surplus
+        if surplus > 0:                  # ... and neither the replay cursor nor the Philox counter remembers them; with no
+            self._hot_counter = self._hot.counter - surplus      # surplus the loop is still in step with both and stays open
             self._hot.close()
             self._hot = None
-            self._rewind_ring(passes - n_steps)
+            self._rewind_ring(surplus)
             if per is not None:
-                per.n_entries = ring.filled * self.backend.N
-        tr.loss = tr.learner.loss
-        item = {"loss": tr.learner.loss, "sum_epoch": tr.epoch, "score": uav.score, "average_score": uav.score,
-                "step": uav.Step, "energy_cost": uav.energy_cost_total, "task_collect": uav.task_collect,
-                "Energy_Efficent": uav.task_collect / (uav.energy_cost_total + 0.001), "UE_waiting_time": 0}
-        self.Train_statistics([item])
-        if tr.Is_Train and tr.epoch // tr.save_loop != getattr(self, "_saved_at", 0):   # save() as _learn does, per save_loop updates
-            self._saved_at = tr.epoch // tr.save_loop
-            tr.save()
-        self.steps_last_episode = n_steps
-        self.epoch += 1
-        if self.epoch % self.print_loop == 0:
-            uav.record_list()
-        self._federated_merge()
-        return self.result
+                per.n_entries = ring.filled * self.backend.N     # one tree over every agent's transitions: N per frame
+        return self._end_episode([self._trainer_item(uav, saved_on=self)], n_steps, record=[uav])
 
     def _run_eposide_fused_slots(self, eps_rate):
         """run_eposide with one fused DQN-family trainer per UAV slot (<fused_slots>1</fused_slots>, num_UAV > 1):
@@ -705,16 +789,10 @@ class PathPlan_City:
         each step moved and the info counts, as _run_eposide_fused; updates behind a step that moved nobody are gated off on the
         device, and the counters follow."""
         from dqn_based_uav_3d_path_planer_amd.loop import DQNSlotsHotLoop
-        self.Reset_Result(eps_rate)
-        ring, U = self._ring, self.num_UAV
+        ring = self._ring
         trs = [u.Trainer for u in self.Agents]
         Ls = [t_.learner for t_ in trs]
-        self._episode += 1
-        self._refresh_bank()
-        self.backend.reset(self.seed + self._episode, obs=ring.obs[ring.head])      # UAV.reset everywhere; the replay stays
-        self._obs_raw = ring.obs[ring.head]
-        self._invalidate()
-        self._paths, self._path_done = [[] for _ in range(U)], [False] * U
+        k = self._begin_fused_episode(eps_rate)
         train = all(t_.Is_Train for t_ in trs)
         batch_now = trs[0].Batch_Size if train else 0
         if self._slots_hot is not None and not self._slots_hot.in_sync(batch_now):
@@ -731,66 +809,33 @@ class PathPlan_City:
         self.slots_loop_with_per = pers is not None
         beta0 = pers[0].beta if pers is not None else None
         hot.set_eps(eps_rate if train else 0.0)
-        k = 1 if self.record_path else min(self.done_check, ring.frames - 2)
         n_steps, ended, passes = 0, False, 0
-        dev = self.backend.device
         epoch0 = [L.epoch for L in Ls]
         while not ended:
             t0 = ring.head
             hot.run(k)
             passes += k
-            fr = (t0 + torch.arange(k, device=dev)) % ring.frames
-            v = ring.valid[fr].bool()                                                # [k, N] agents moved by each step
-            inf = self._info[fr]
-            stats = torch.cat([torch.stack([v.sum(1)] + [((inf == c) & v).sum(1) for c in range(3)], 1),
-                               v.view(k, -1, U).sum(1)], 1).cpu().numpy()            # one sync; columns 4..: moved per UAV slot
-            for i in range(k):
-                if stats[i, 0] == 0:                                                 # nobody moved: finished before this step
-                    ended = True
-                    break
-                n_steps += 1
-                self.result["normal"] += int(stats[i, 1])
-                self.result["success"] += int(stats[i, 2])
-                self.result["lose"] += int(stats[i, 3])
-                for j in range(U):                                                   # (the selective merge's 10-transition rule)
-                    self._fl_slot_valid[j] += int(stats[i, 4 + j])
-            self._obs_raw = ring.obs[ring.head]
-            self._invalidate()
-            if self.record_path:
-                self._record_paths(range(U))
+            n, ended, moved_of_slot = self._tally_chunk(self._read_chunk(t0, k, per_slot=True))
+            n_steps += n
+            for j, m in enumerate(moved_of_slot):                                    # (the selective merge's 10-transition rule)
+                self._fl_slot_valid[j] += m
+            self._after_chunk()
         surplus = passes - n_steps
         for L, e0 in zip(Ls, epoch0):        # the gated passes changed nothing on the device: one update per moving step
             L.epoch -= min(surplus, L.epoch - e0)
-        if pers is not None:                 # (beta moves with every update; every slot took the same number)
-            for p in pers:
+        if pers is not None:                 # (always, unlike the single-net loop: the closed form over the updates that count
+            for p in pers:                   #  replaces the loop's running beta even when nothing was undone; every slot took as many)
                 p.beta = min(1.0, beta0 + (Ls[0].epoch - epoch0[0]) * p.beta_inc)
         self.surplus_passes_last_episode = surplus
-        self._slots_counter = hot.counter - surplus
+        self._slots_counter = hot.counter - surplus              # (always: the next loop object, if one is made, starts from it)
         if surplus > 0:                      # ... and neither the replay cursor nor the Philox counter remembers them
             hot.close()
             self._slots_hot = None
             self._rewind_ring(surplus)
             if pers is not None:
                 for p in pers:
-                    p.n_entries = ring.filled * self.num_envs
-        items = []
-        for uav in self.Agents:
-            tr = uav.Trainer
-            tr.loss = tr.learner.loss
-            items.append({"loss": tr.learner.loss, "sum_epoch": tr.epoch, "score": uav.score, "average_score": uav.score,
-                          "step": uav.Step, "energy_cost": uav.energy_cost_total, "task_collect": uav.task_collect,
-                          "Energy_Efficent": uav.task_collect / (uav.energy_cost_total + 0.001), "UE_waiting_time": 0})
-            if tr.Is_Train and tr.epoch // tr.save_loop != getattr(tr, "_saved_at", 0):
-                tr._saved_at = tr.epoch // tr.save_loop
-                tr.save()
-        self.Train_statistics(items)
-        self.steps_last_episode = n_steps
-        self.epoch += 1
-        if self.epoch % self.print_loop == 0:
-            for uav in self.Agents:
-                uav.record_list()
-        self._federated_merge()
-        return self.result
+                    p.n_entries = ring.filled * self.num_envs    # one tree per UAV slot: num_envs of its transitions per frame
+        return self._end_episode([self._trainer_item(uav, saved_on=uav.Trainer) for uav in self.Agents], n_steps)
 
     def _run_eposide_fused_sac(self, eps_rate):
         """run_eposide with one fused SAC trainer per UAV slot (BASELINE configs[3]'s shape): per time step, one
@@ -799,15 +844,8 @@ class PathPlan_City:
         Nothing is read back inside the loop except, every done_check steps, how many agents each step moved and the info
         counts (as _run_eposide_fused; the same up-to-done_check - 1 surplus updates at the end of an episode)."""
         from dqn_based_uav_3d_path_planer_amd import _lib
-        self.Reset_Result(eps_rate)
         ring, U, N = self._ring, self.num_UAV, self.backend.N
-        self._episode += 1
-        self._refresh_bank()
-        self.backend.reset(self.seed + self._episode, obs=ring.obs[ring.head])
-        self._obs_raw = ring.obs[ring.head]
-        self._invalidate()
-        self._paths, self._path_done = [[] for _ in range(U)], [False] * U
-        k = 1 if self.record_path else min(self.done_check, ring.frames - 2)
+        k = self._begin_fused_episode(eps_rate)
         dev = self.backend.device
         lib = self.backend.lib
         act0, act1 = ring.action.view(-1), self._a1.view(-1)
@@ -913,27 +951,15 @@ class PathPlan_City:
             if use_c:
                 self._sac_hot.run(k)
                 self._sac_counter = self._sac_hot.counter
-            fr = (t0 + torch.arange(k, device=dev)) % ring.frames
-            v = ring.valid[fr].bool()
-            inf = self._info[fr]
-            stats = torch.stack([v.sum(1)] + [((inf == c) & v).sum(1) for c in range(3)], 1).cpu().numpy()   # one sync
-            moved = stats[:, 0]
+            stats = self._read_chunk(t0, k)
+            moved = None
             if multi:               # a step counts while ANY rank still moves an agent: the ranks leave the episode together
                 every = [None] * torch.distributed.get_world_size()
-                torch.distributed.all_gather_object(every, [int(x) for x in moved])
+                torch.distributed.all_gather_object(every, [int(x) for x in stats[:, 0]])
                 moved = np.sum(np.asarray(every, dtype=np.int64), axis=0)
-            for i in range(k):
-                if moved[i] == 0:
-                    ended = True
-                    break
-                n_steps += 1
-                self.result["normal"] += int(stats[i, 1])
-                self.result["success"] += int(stats[i, 2])
-                self.result["lose"] += int(stats[i, 3])
-            self._obs_raw = ring.obs[ring.head]
-            self._invalidate()
-            if self.record_path:
-                self._record_paths(range(U))
+            n, ended, _ = self._tally_chunk(stats, moved)
+            n_steps += n
+            self._after_chunk()
         if gate_local:
             _lib.check(lib.uavenv_set_moved_word(self.backend._h, None), "uavenv_set_moved_word")
         for L in Ls:
@@ -948,7 +974,7 @@ class PathPlan_City:
                     p.beta = min(1.0, beta0[j] + (L.adam_steps - count0[j][1]) * p.beta_inc)
         self.surplus_passes_last_episode = surplus
         if surplus > 0:
-            if not multi:
+            if not multi:                    # (several ranks: the noise of the surplus steps was drawn and used)
                 self._sac_counter -= surplus
             if getattr(self, "_sac_hot", None) is not None:
                 self._sac_hot.close()
@@ -956,26 +982,9 @@ class PathPlan_City:
             self._rewind_ring(surplus)
             for p in self._sac_per:
                 if p is not None:
-                    p.n_entries = ring.filled * self.num_envs
-        items = []
-        for uav in self.Agents:
-            tr = uav.Trainer
-            tr.loss = tr.learner.loss
-            items.append({"loss": tr.learner.loss, "sum_epoch": tr.epoch, "score": uav.score, "average_score": uav.score,
-                          "step": uav.Step, "energy_cost": uav.energy_cost_total, "task_collect": uav.task_collect,
-                          "Energy_Efficent": uav.task_collect / (uav.energy_cost_total + 0.001), "UE_waiting_time": 0})
-            if tr.Is_Train and tr.epoch // tr.save_loop != getattr(tr, "_saved_at", 0):
-                tr._saved_at = tr.epoch // tr.save_loop
-                tr.save()
-        self.Train_statistics(items)
-        self.steps_last_episode = n_steps
+                    p.n_entries = ring.filled * self.num_envs    # one tree per UAV slot, as in the DQN slots loop
         self.sac_c_loop_used = bool(use_c)          # (tests: which of the two issue paths ran)
-        self.epoch += 1
-        if self.epoch % self.print_loop == 0:
-            for uav in self.Agents:
-                uav.record_list()
-        self._federated_merge()
-        return self.result
+        return self._end_episode([self._trainer_item(uav, saved_on=uav.Trainer) for uav in self.Agents], n_steps)
 
     def _run_eposide_on_policy(self, eps_rate=0.1):
         """PathPlan_City.py:419-436 + run_thread_OnPolicy (:386-406), for all vectorised envs at once: per time step every UAV that is
@@ -985,7 +994,6 @@ class PathPlan_City:
         interact, so the result is that of the loop below.)"""
         self.Reset_Result(eps_rate)
         self.Scene_Random_Reset()
-        names = ("normal", "success", "lose")
         keys = ("states", "actions", "next_states", "rewards", "dones")
         acc = [{k: [] for k in keys} for _ in self.Agents]
         while True:
@@ -993,23 +1001,7 @@ class PathPlan_City:
             states = self._obs
             s_view = states.view(self.num_envs, self.num_UAV, -1)
             chosen = [uav.Trainer.get_action_batch(s_view[:, j], eps_rate).to(states.device) for j, uav in enumerate(self.Agents)]
-            continuous = any(c.dim() == 2 for c in chosen)
-            actions = torch.zeros((self.num_envs, self.num_UAV), dtype=torch.float32 if continuous else torch.int32, device=states.device)
-            for j, c in enumerate(chosen):
-                if c.dim() == 2:
-                    actions[:, j] = c[:, 0].float()
-                elif continuous:
-                    actions[:, j] = -1.0 + 2.0 * c.float() / (self.Agents[j].Trainer.act_num - 1)
-                else:
-                    actions[:, j] = c.to(torch.int32)
-            out = self.backend.step(actions.reshape(-1).contiguous(), skip_done=True)     # `if uav.done: return` (:388-389)
-            self._obs = out.obs
-            self._invalidate()
-            self._record_paths(range(self.num_UAV))
-            info = out.info.view(self.num_envs, self.num_UAV)
-            valid = out.valid.view(self.num_envs, self.num_UAV).bool()
-            for k, nm in enumerate(names):
-                self.result[nm] += int(((info == k) & valid).sum().item())                # Run_statistics (:395)
+            out, valid = self._step_chosen(chosen)
             n_view = out.obs.view(self.num_envs, self.num_UAV, -1)
             r_view = out.reward32.view(self.num_envs, self.num_UAV)
             d_view = out.ret_done.view(self.num_envs, self.num_UAV)
@@ -1025,14 +1017,7 @@ class PathPlan_City:
                 break
         for j, uav in enumerate(self.Agents):
             uav.transition_dict = {k: torch.cat(acc[j][k]) for k in keys}
-        train_info = self.update()                                                        # :436, after the episode
-        self.Train_statistics(train_info)
-        self.epoch += 1
-        if self.epoch % self.print_loop == 0:
-            for uav in self.Agents:
-                uav.record_list()
-        self._federated_merge()
-        return self.result
+        return self._end_episode(self.update())                                           # :436, after the episode
 
     def run_eposide(self, eps_rate=0.1):
         """PathPlan_City.py:410-478 (off-policy branch) for all vectorised envs at once: reset, then
@@ -1047,7 +1032,6 @@ class PathPlan_City:
             return self._run_eposide_fused_slots(eps_rate)
         self.Reset_Result(eps_rate)
         self.Scene_Random_Reset()
-        names = ("normal", "success", "lose")
         train_info = []
         while True:
             self.run()
@@ -1057,24 +1041,7 @@ class PathPlan_City:
             for j, uav in enumerate(self.Agents):
                 uav.transition_dict = {"states": [], "actions": [], "next_states": [], "rewards": [], "dones": []}
                 chosen.append(uav.Trainer.get_action_batch(s_view[:, j], eps_rate).to(states.device))
-            continuous = any(c.dim() == 2 for c in chosen)          # SAC: [n, action_dim], only [:, 0] steers (UAV.py:414)
-            actions = torch.zeros((self.num_envs, self.num_UAV), dtype=torch.float32 if continuous else torch.int32,
-                                  device=states.device)
-            for j, c in enumerate(chosen):
-                if c.dim() == 2:
-                    actions[:, j] = c[:, 0].float()
-                elif continuous:                                     # mixed: index -> steer with the documented table
-                    actions[:, j] = -1.0 + 2.0 * c.float() / (self.Agents[j].Trainer.act_num - 1)
-                else:
-                    actions[:, j] = c.to(torch.int32)
-            out = self.backend.step(actions.reshape(-1).contiguous(), skip_done=True)     # done agents wait (:365-366)
-            self._obs = out.obs
-            self._invalidate()
-            self._record_paths(range(self.num_UAV))
-            info = out.info.view(self.num_envs, self.num_UAV)
-            valid = out.valid.view(self.num_envs, self.num_UAV).bool()
-            for k, nm in enumerate(names):
-                self.result[nm] += int(((info == k) & valid).sum().item())
+            out, valid = self._step_chosen(chosen)
             n_view = out.obs.view(self.num_envs, self.num_UAV, -1)
             r_view = out.reward32.view(self.num_envs, self.num_UAV)
             d_view = out.ret_done.view(self.num_envs, self.num_UAV)
@@ -1090,10 +1057,4 @@ class PathPlan_City:
             train_info = self.update()                                                        # :456
             if self.Check_uav_Done():
                 break
-        self.Train_statistics(train_info)
-        self.epoch += 1
-        if self.epoch % self.print_loop == 0:
-            for uav in self.Agents:
-                uav.record_list()
-        self._federated_merge()
-        return self.result
+        return self._end_episode(train_info)

@@ -430,7 +430,7 @@ def test_fresh_plans_between_episodes(tmp_path, monkeypatch):
     assert np.array_equal(env2.backend.bank_read()[0], b0) and env2.backend.replan_stats()["refreshes"] == 0
 
 
-@pytest.mark.parametrize("trainer", ["DQN", "SAC"])
+@pytest.mark.parametrize("trainer", ["DQN", "SAC", "DQN_slots"])
 def test_done_check_does_not_change_what_is_learnt(trainer, tmp_path, monkeypatch):
     """The fused episode paths look at the device only every <done_check> steps, so up to done_check - 1 passes are enqueued
     behind the last moving step.  Round 4: those passes change nothing -- the step kernel stamps a device word when it moves
@@ -447,13 +447,19 @@ def test_done_check_does_not_change_what_is_learnt(trainer, tmp_path, monkeypatc
         torch.manual_seed(0)                          # the same initial weights in both runs
         if trainer == "SAC":
             sim = _config4(tmp_path, 128, Batch_Size=128, replay_size=400000)
+        elif trainer == "DQN_slots":                  # one fused learner per UAV slot, uniform replay; 512 agents: twice the ring
+            xml = driver.make_config_dir(str(tmp_path), "DQN", num_envs=256, num_uav=2)
+            s = open(xml).read()
+            open(xml, "w").write(s.replace("<seed>42</seed>", "<seed>42</seed>\n        <fused_slots>1</fused_slots>"))
+            _set_xml(tmp_path / "config" / "Trainer.xml", replay_size=1600000)
+            sim = driver.simulator(xml)
         else:
             xml = driver.make_config_dir(str(tmp_path), "DQN", num_envs=256, num_uav=1)
             _set_xml(tmp_path / "config" / "Trainer.xml", replay_size=800000)
             sim = driver.simulator(xml)
         env = sim.env
         env.done_check = dc
-        assert env.fast or env.fast_sac
+        assert env.fast_slots if trainer == "DQN_slots" else (env.fast or env.fast_sac)
         torch.manual_seed(0)
         for _ in range(2):
             env.run_eposide(0.2)
@@ -462,6 +468,9 @@ def test_done_check_does_not_change_what_is_learnt(trainer, tmp_path, monkeypatc
             L = [u.Trainer.learner for u in env.Agents]
             blocks = [torch.cat([x._blocks.reshape(-1), x._cblocks.reshape(-1), x._alpha_mv, x.log_alpha.reshape(1)]).clone() for x in L]
             counts = [(x.epoch, x.adam_steps) for x in L]
+        elif trainer == "DQN_slots":
+            L = [u.Trainer.learner for u in env.Agents]
+            blocks, counts = [x.flat.clone() for x in L], [(x.epoch,) for x in L]
         else:
             L = env.Agents[0].Trainer.learner
             blocks, counts = [L.flat.clone()], [(L.epoch,)]
