@@ -475,93 +475,8 @@ __device__ __forceinline__ ObsBits obs_cand_queued(const WorldLds<MaskT> &w, Obs
     return o;
 }
 
-// ---- one stencil per wavefront (the cooperative small-N kernel) ---------------------------------------------------
-// Stencil k (spacing kSp[k]) of state_PathPlan for the 64 agents of a workgroup, by ONE wavefront: the same
-// classify -> queue -> dense 25-point tests as obs_bits_queued, but over the stencil's own halo grid g[k] (fewer
-// candidates than the widest grid) and with a single test per candidate.  pos = LDS [64][4] doubles (x, y, z, pad),
-// acc = LDS [64] words this function zeroes and ORs into.  Same exact tests on the same operands => the same bits.
-template <typename MaskT>
-__device__ __forceinline__ void stencil_queue_drain(const WorldLds<MaskT> &w, const uint32_t *queue, uint32_t *acc,
-                                                    const double *pos, double sp, int count)
-{
-    const int lane = (int)threadIdx.x & 63;
-    wave_lds_sync();
-    for (int base = 0; base < count; base += 64) {
-        const int it = base + lane;
-        if (it < count) {
-            const uint32_t item = queue[it];
-            const int owner = (int)(item & 63u), b = (int)(item >> 6);
-            const double px = pos[owner * 4], py = pos[owner * 4 + 1];
-            const BldLds B = w.b[b];
-            double dx2[5], dy2[5];
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                const double dx = (px + sp * (double)(i - 2)) - B.cx, dy = (py + sp * (double)(i - 2)) - B.cy;
-                dx2[i] = dx * dx;
-                dy2[i] = dy * dy;
-            }
-            uint32_t bk = 0;
-#pragma unroll
-            for (int i = 0; i < 5; ++i)
-#pragma unroll
-                for (int j = 0; j < 5; ++j) bk |= ((dx2[i] + dy2[j]) < B.thr) ? (1u << (5 * i + j)) : 0u;
-            if (bk) atomicOr(&acc[owner], bk);
-        }
-    }
-    wave_lds_sync();
-}
-
-// `subset` selects which candidate cylinders this wavefront handles (all ones: every candidate); two wavefronts with
-// complementary subsets split one stencil between them and OR their results.
-template <typename MaskT>
-__device__ __forceinline__ uint32_t obs_stencil_queued(const WorldLds<MaskT> &w, uint32_t *queue, uint32_t *acc,
-                                                       const double *pos, int k, double px, double py, double pz,
-                                                       bool active, MaskT subset)
-{
-    const int lane = (int)threadIdx.x & 63;
-    const double sp = k == 0 ? 1.0 : (k == 1 ? 5.0 : 10.0);
-    uint32_t mine = 0;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const double xi = px + sp * (double)(i - 2), yi = py + sp * (double)(i - 2);
-        mine |= ((xi < 0.0) | (xi > w.W)) ? (0x1Fu << (5 * i)) : 0u;
-        mine |= ((yi < 0.0) | (yi > w.W)) ? (0x108421u << i) : 0u;
-    }
-    if ((pz < 0.0) | (pz > w.Hbox)) mine = 0x1FFFFFFu;
-    acc[lane] = 0u;
-    MaskT m = active ? (MaskT)(w.g[k][cell_of(w, px, py)] & subset) : (MaskT)0;
-    int count = 0;                                   // wave-uniform
-    while (__ballot(m != 0) != 0ull) {
-        if (count > kObsQueueCap - 64) {
-            stencil_queue_drain(w, queue, acc, pos, sp, count);
-            count = 0;
-        }
-        const bool have = m != 0;
-        const int b = have ? ctz_mask(m) : 0;
-        if (have) m &= (MaskT)(m - 1);
-        bool full = false;
-        if (have) {
-            const BldLds B = w.b[b];
-            const double rej2 = w.aux[b].rej2[k], acc2 = w.aux[b].acc2[k];
-            const double dcx = px - B.cx, dcy = py - B.cy;
-            const double dc2 = dcx * dcx + dcy * dcy;
-            if (!(pz > B.H)) {
-                if (dc2 < acc2) mine = 0x1FFFFFFu;                  // stencil entirely inside the disc
-                else if (dc2 < rej2) full = true;                   // can touch: needs the 25 exact tests
-            }
-        }
-        const unsigned long long bm = __ballot(full);
-        if (bm) {
-            const int at = count + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32),
-                                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
-            if (full) queue[at] = (uint32_t)lane | ((uint32_t)b << 6);
-            count += __builtin_popcountll(bm);
-        }
-    }
-    stencil_queue_drain(w, queue, acc, pos, sp, count);
-    return mine | acc[lane];
-}
-
+// The cooperative small-N kernel (k_step_coop): wavefronts 1..3 run obs_cand_queued (phase = wave - 1) plus the
+// obs_box_bits of one stencil each; wavefront 0 adds the below part, which needs no queue.
 // UAV.py:562-566: Threaten_rate(px, py, pz - k), k = 1..5 (all 1 while the UAV is on the ground: z - k < 0)
 template <typename MaskT>
 __device__ __forceinline__ uint32_t obs_below_bits(const WorldLds<MaskT> &w, double px, double py, double pz)
