@@ -667,12 +667,15 @@ __device__ __forceinline__ void step_post_a(const StepArgs &a, const WorldLds<Ma
     M.r = r;
 }
 
-// Adjust_subgoal (:156-166) for ONE agent by its own lane (private list only)
-__device__ __forceinline__ void adjust_subgoals_lane(const StepArgs &a, int ii, Agent &g)
+// Adjust_subgoal (:156-166) for ONE agent by its own lane (private list only).  `pre_alias`: the alias flag before the move.
+// While sub_goals[0] was the position object it moved with it (:419-420), and a collision on this step only rebinds
+// `position` (:427): the list still holds the moved-to point, which is the operand here -- the window has it, the stored
+// entry does not.
+__device__ __forceinline__ void adjust_subgoals_lane(const StepArgs &a, int ii, Agent &g, bool pre_alias)
 {
     ObsIn &o = g.o;
     double *lst = a.st.sub + (size_t)ii * a.K * 3;
-    if (g.alias) { lst[g.sub_idx * 3] = o.s0x; lst[g.sub_idx * 3 + 1] = o.s0y; lst[g.sub_idx * 3 + 2] = o.s0z; }
+    if (pre_alias) { lst[g.sub_idx * 3] = o.s0x; lst[g.sub_idx * 3 + 1] = o.s0y; lst[g.sub_idx * 3 + 2] = o.s0z; }
     for (int k = g.sub_idx; k < g.n_total; ++k) {
         double fx, fy, fz;
         const double sx = lst[k * 3], sy = lst[k * 3 + 1], sz = lst[k * 3 + 2];
@@ -871,8 +874,8 @@ __device__ __forceinline__ void adjust_subgoals_split(const StepArgs &a, int ii,
     ObsIn &o = g.o;
     double *lst = a.st.sub + ((size_t)ii * a.K + g.sub_idx) * 3;
     if (pre_alias) {
-        // (a collision this step ended the alias before the adjustment: then the list's own entry is the operand)
-        const double sx = g.alias ? o.s0x : lst[0], sy = g.alias ? o.s0y : lst[1], sz = g.alias ? o.s0z : lst[2];
+        // (the window, not the stored entry: it holds the moved-to point, also where a collision this step ended the alias)
+        const double sx = o.s0x, sy = o.s0y, sz = o.s0z;
         double fx, fy, fz;
         cal_force(a, sx, sy, sz, fx, fy, fz);
         o.s0x = sx + fx; o.s0y = sy + fy; o.s0z = sz + fz;
@@ -955,8 +958,9 @@ __device__ __forceinline__ void step_post(const StepArgs &a, const WorldLds<Mask
                                           const PreStep &P, double &r, int &ret_done, int &info, bool &head_set)
 {
     PostMid M;
+    const bool pre_alias = g.alias != 0;
     step_post_a<MaskT, APF, INL>(a, w, ii, a0, g, P, M, ret_done, info, head_set);
-    if (APF && M.live) adjust_subgoals_lane(a, ii, g);
+    if (APF && M.live) adjust_subgoals_lane(a, ii, g, pre_alias);
     step_post_b<MaskT, APF, INL>(a, w, ii, g, M, r, ret_done, info, head_set);
 }
 

@@ -6,6 +6,7 @@ and bench.py never need the reference at run time.
 
     python oracle/gen_golden.py            # env-path goldens
     python oracle/gen_golden.py --learner  # trainer goldens (see gen_golden_learner.py)
+    python oracle/gen_golden.py --cascade-edges   # cascade_edges.npz alone
 
 What pins what (reference file:line):
   world_stock.npz      config/buildings.xml, config/UAV.xml, config/PathPlan_City.xml as parsed by the reference
@@ -15,6 +16,8 @@ What pins what (reference file:line):
   episodes.npz         Agents/UAV.py:397-567 whole episodes from reset, scripted actions
   injected.npz         Agents/UAV.py:397-567 single steps from injected states (all branches)
   apf.npz              Agents/UAV.py:156-210,448-453 with building.v injected
+  cascade_edges.npz    Agents/UAV.py:397-513 two steps from every state of tests/cascade_edges.py: the termination cascade with
+                       every distance on its threshold and on the neighbouring doubles (max_v = 0, or heading and action 0)
   apf_episodes.npz     the same, WHOLE episodes from uav.reset() with APF_Enabled = 1: every step's outputs, state and the
                        full sub-goal list (Adjust_subgoal shifts every sub-goal every step: accumulated drift is compared)
 """
@@ -410,8 +413,62 @@ def gen_apf_episodes(s, out, kmax=48):
           "lens", [len(e["actions"]) for e in eps], "skipped seeds (reference raised)", skipped)
 
 
+def gen_cascade_edges(s, out):
+    """The catalogue of tests/cascade_edges.py through the executed reference, two update_PathPlan calls per case.  Data only:
+    the inputs (so that the host test can tell a catalogue that has drifted from its golden) and the recorded outputs."""
+    sys.path.insert(0, os.path.join(HERE, "..", "tests"))
+    import cascade_edges as ce
+    uav, Loc = s.uav, s.CalMod.Loc
+    b = np.array([[t.position.x, t.position.y, t.position.z, t._R, t._H] for t in s.env.buildings], dtype=np.float64)
+    cat = ce.build(b)
+    stock_v, stock_step = uav.Max_V, uav.Max_Step
+    save = {}
+    for name, grp in cat.items():
+        uav.Max_V, uav.Max_Step = grp.max_v, ce.MAX_STEP
+        for key, a in (("kin", grp.kin), ("step0", grp.step0), ("n_sub", grp.n_sub), ("sub_goals", grp.sub), ("alias0", grp.alias),
+                       ("actions", grp.action)):
+            save[name + "_" + key] = a
+        # APF off, then APF on over buildings at rest (cal_force skips every one of them, :180-182; Adjust_subgoal still rebuilds
+        # the list from new objects, which is what ends the alias)
+        for apf, prefix in ((0, "_out_"), (1, "_apf_out_")):
+            if apf:
+                for t in s.env.buildings:
+                    t.v = Loc(0.0, 0.0, 0.0)
+            res = ce.empty_outputs(grp.n, grp.K)
+            for c in range(grp.n):
+                k = grp.kin[c]
+                n = int(grp.n_sub[c])
+                inject(s, [k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], int(grp.step0[c])], grp.sub[c, :n], apf=apf)
+                if grp.alias[c]:                # the first step after a reset: sub_goals[0] IS the position object (RRT.py:69)
+                    assert tuple(grp.sub[c, 0]) == (k[0], k[1], k[2])
+                    uav.sub_goals[0] = uav.position
+                for t in range(ce.STEPS):
+                    r, d, info = uav.update([float(grp.action[c]), 0.0])
+                    res["reward"][c, t], res["ret_done"][c, t], res["info"][c, t] = f(r), int(d), INFO[info]
+                    res["state"][c, t] = uav_state_vec(uav)
+                    res["sub"][c, t] = subgoals_arr(uav, grp.K)
+                    res["alias"][c, t] = int(len(uav.sub_goals) > 0 and uav.sub_goals[0] is uav.position)
+            if apf:
+                uav.APF_Enabled = 0
+                for t in s.env.buildings:
+                    del t.v
+            for key, a in res.items():
+                save[name + prefix + key] = a
+            print("cascade_edges", name, "APF", apf, grp.n, "cases; info counts of the first step",
+                  {k: int((res["info"][:, 0] == k).sum()) for k in (0, 1, 2)})
+    uav.Max_V, uav.Max_Step = stock_v, stock_step
+    np.savez_compressed(os.path.join(out, "cascade_edges.npz"), **save)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if "--cascade-edges" in sys.argv[1:]:       # this golden alone
+        s = RefSession()
+        try:
+            gen_cascade_edges(s, OUT)
+        finally:
+            s.close()
+        return
     s = RefSession()
     try:
         b = gen_world(s, OUT)
@@ -422,6 +479,7 @@ def main():
         gen_injected(s, OUT, 3000)
         gen_apf(s, OUT, 600)
         gen_apf_episodes(s, OUT)
+        gen_cascade_edges(s, OUT)
     finally:
         s.close()
 
