@@ -81,6 +81,7 @@ class UavDqnNet(C.Structure):
 # uavenv_eval_episodes (include/uavenv.h): outcome codes, the 64-byte per-episode record and the call's arguments
 EVAL_SUCCESS, EVAL_LOSE, EVAL_TRUNCATED, EVAL_INVALID = 1, 2, 4, 5
 EVAL_RECORD_BYTES = 64
+EVAL_MAX_OUTPUTS = 14              # UAVENV_EVAL_MAX_OUTPUTS: layer-2 outputs (n_actions + dueling) the f32 entries take; the f16 entry: 4
 
 
 class UavEvalRecord(C.Structure):

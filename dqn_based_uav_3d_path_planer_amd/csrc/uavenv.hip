@@ -1815,6 +1815,77 @@ __device__ __forceinline__ int eval_dqn_action(const float (&q)[4], int A, float
     return eval_eps_action(act, A, eps, seed, e, step);
 }
 
+// ---- heads of 5 .. UAVENV_EVAL_MAX_OUTPUTS layer-2 outputs (k_eval_episodes<.., true>, k_eval_episodes_slots<.., .., true>).
+// What the forward hands the kernel: float[4] Q values, or -- wide -- the lane's greedy action, taken inside the strip loop: a
+// W2Frag of 14 rows is 238 registers beside an Agent in f64, and 14 Q values kept per lane across the strips cost 14 more.
+static_assert(UAVENV_EVAL_MAX_OUTPUTS == uavq::kMaxOut - 2, "the episode kernels take the heads the act / grad kernels take");
+template <bool WIDE> struct EvalQ { typedef float type[4]; };
+template <> struct EvalQ<true> { typedef int type; };
+
+// eval_forward_f32 for 4 < n2 <= 14: per strip, layer 2 in groups of four outputs (the last of two), each group's fragment from
+// the LDS block eval_stage_w2 filled and dead before the next is loaded.  Raw output o[a] is q_strip_n's own text on rows
+// 4 g .. 4 g + 3 as a plain head (the fmaf chain, (st0 + st1) + (st2 + st3), group_sum4, + b[a]): the bits q_strip_n<14> gives
+// it.  The dueling combination is q_strip_n's in its order, on the 14 raw outputs; the action is policy_select_n's greedy branch
+// on the q[a], not the o[a] (two different o can round to one q).  Lane 16 st + r keeps strip st's action.
+__device__ __forceinline__ void eval_forward_f32(const uavq::W1Split &W1, const float *W2, const float *b2, uint32_t *rows,
+                                                 const uavq::PRow &R, int lane, int n2, int n_actions, int dueling, int &greedy)
+{
+    constexpr int NQ = UAVENV_EVAL_MAX_OUTPUTS;
+    const int r16 = lane & 15, grp = lane >> 4;
+    wave_lds_sync();                                                 // (the queue's last reads are done: the rows take its bytes)
+    uavq::prow_store_lds(rows + lane * kPackedDwords, R);
+    wave_lds_sync();
+    greedy = 0;
+#pragma unroll 1
+    for (int st = 0; st < 4; ++st) {
+        uavq::PRow Rs;
+        uavq::prow_load(Rs, rows + (16 * st + r16) * kPackedDwords);
+        uavq::floatx4 h[4];
+        uavq::fwd_strip_split<false>(W1, Rs, h);
+        float o[NQ];
+#pragma unroll
+        for (int g0 = 0; g0 < NQ; g0 += 4) {
+            float og[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (g0 < n2) {                                           // (wave-uniform)
+                uavq::W2Frag<4> F;
+                uavq::w2_load_n<4>(F, W2 + g0 * uavq::kHid, b2 + g0, n2 - g0);
+                uavq::q_strip_n<4>(h, F, n2 - g0, 4, 0, og);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (g0 + k < NQ) o[g0 + k] = og[k];
+        }
+        float q[NQ];
+        if (dueling) {                                            // Q = V + A - mean(A)   (q_strip_n)
+            float mean = 0.0f, val = 0.0f;
+#pragma unroll
+            for (int a = 0; a < NQ; ++a) {
+                if (a < n_actions) mean += o[a];
+                if (a == n_actions) val = o[a];
+            }
+            mean /= (float)n_actions;
+#pragma unroll
+            for (int a = 0; a < NQ; ++a) q[a] = val + o[a] - mean;
+        } else {
+#pragma unroll
+            for (int a = 0; a < NQ; ++a) q[a] = o[a];
+        }
+        int act = 0;
+        float bq = q[0];
+#pragma unroll
+        for (int k = 1; k < NQ; ++k)
+            if (k < n_actions && q[k] > bq) { bq = q[k]; act = k; }
+        greedy = grp == st ? act : greedy;
+    }
+    wave_lds_sync();                                                 // the rows are read: the next iteration's queue may take the bytes
+}
+
+// eval_dqn_action of a wide lane: the first maximum is the forward's, the exploration draw the same
+__device__ __forceinline__ int eval_dqn_action(int greedy, int A, float eps, uint64_t seed, int e, int step)
+{
+    return eval_eps_action(greedy, A, eps, seed, e, step);
+}
+
 // update_PathPlan (UAV.py:397-513, step_agent's pieces) of episode L.e with the decoded action a0, and the episode's accounting.
 // The sub-goal list is the resident lane's own with APF (`li`, as eval_install), else the episode's scenario row; j = L.e mod U is
 // the UAV slot.  Stores the trajectory position; true when the step lies inside the trajectory window (the kernel then stores its
@@ -1857,7 +1928,7 @@ __device__ __forceinline__ bool eval_episode_end(const EvalRun &v, const Agent &
     return true;
 }
 
-template <typename MaskT>
+template <typename MaskT, bool WIDE = false>   // WIDE: heads of more than 4 layer-2 outputs (EvalQ, the second eval_forward_f32)
 __global__ void __launch_bounds__(256, 1) k_eval_episodes(StepArgs a, EvalArgs v)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1888,7 +1959,7 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes(StepArgs a, EvalArgs v
         if (__ballot(L.e < run.n) == 0ull) break;
         const bool have = L.e < run.n;
         const uavq::PRow R = eval_obs_row(w, Q, g, have);
-        float q[4];
+        typename EvalQ<WIDE>::type q;
         eval_forward_f32(W1, W2, b2, rows, R, lane, v.n2, A, v.dueling, q);
         if (have) {
             const int act = eval_dqn_action(q, A, v.eps, run.seed, L.e, L.steps);
@@ -2099,7 +2170,7 @@ struct SlotsEvalArgs {
     int32_t n2, dueling;
 };
 
-template <typename MaskT, bool APF>
+template <typename MaskT, bool APF, bool WIDE = false>   // WIDE: as k_eval_episodes
 __global__ void __launch_bounds__(256, 1) k_eval_episodes_slots(StepArgs a, SlotsEvalArgs v)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -2132,7 +2203,7 @@ __global__ void __launch_bounds__(256, 1) k_eval_episodes_slots(StepArgs a, Slot
         if (__ballot(L.e < run.n) == 0ull) break;
         const bool have = L.e < run.n;
         const uavq::PRow R = eval_obs_row(w, Q, g, have);
-        float q[4];
+        typename EvalQ<WIDE>::type q;
         eval_forward_f32(W1, W2, b2, rows, R, lane, v.n2, A, v.dueling, q);
         if (have) {
             const int act = eval_dqn_action(q, A, v.eps, run.seed, L.e, L.steps);
@@ -3221,18 +3292,19 @@ static int eval_check_common(const char *name, const UavEnv *e, const U &u, cons
     return UAVENV_OK;
 }
 
-// a DQN net the episode kernels take: the MFMA kind wanted, the uavenv_step_policy shape, at most 4 layer-2 outputs.  k >= 0: net k of several
-static int eval_check_dqn_net(const char *name, int k, const UavEnv *e, const UavDqnNet *net, int mfma_dtype)
+// a DQN net the episode kernels take: the MFMA kind wanted, the uavenv_step_policy shape, at most max_out layer-2 outputs (the f32
+// entries: UAVENV_EVAL_MAX_OUTPUTS; the f16 entry: 4, all an f16-MFMA learner can have).  k >= 0: net k of several
+static int eval_check_dqn_net(const char *name, int k, const UavEnv *e, const UavDqnNet *net, int mfma_dtype, int max_out)
 {
     const int n2 = net->n_actions + (net->dueling ? 1 : 0);
-    if (net->local && net->mfma_dtype == mfma_dtype && net->w == uavq::kW && net->hid == uavq::kHid && net->n_actions >= 2 && n2 <= 4 &&
+    if (net->local && net->mfma_dtype == mfma_dtype && net->w == uavq::kW && net->hid == uavq::kHid && net->n_actions >= 2 && n2 <= max_out &&
         net->n_actions == e->cfg.n_actions)
         return UAVENV_OK;
     char who[96];
     if (k >= 0) snprintf(who, sizeof(who), "%s: net %d", name, k);
     else snprintf(who, sizeof(who), "%s", name);
-    return fail(UAVENV_EINVAL, "%s: needs an %s-MFMA net of w %d, hid %d, the env's %d actions, <= 4 outputs", who,
-                mfma_dtype == UAVENV_MFMA_F16 ? "f16" : "f32", uavq::kW, uavq::kHid, e->cfg.n_actions);
+    return fail(UAVENV_EINVAL, "%s: needs an %s-MFMA net of w %d, hid %d, the env's %d actions, <= %d outputs", who,
+                mfma_dtype == UAVENV_MFMA_F16 ? "f16" : "f32", uavq::kW, uavq::kHid, e->cfg.n_actions, max_out);
 }
 
 // the env's parameters and world; the scenario set in the bank's place; nothing the step launches own
@@ -3346,11 +3418,13 @@ int uavenv_eval_episodes(UavEnv *e, const UavDqnNet *net, const UavEvalArgs *arg
     static const char *const name = "uavenv_eval_episodes";
     static const EvalKernels kernels = {{{reinterpret_cast<const void *>(k_eval_episodes<uint64_t>), nullptr},
                                          {reinterpret_cast<const void *>(k_eval_episodes<uint32_t>), nullptr}}};
+    static const EvalKernels wide = {{{reinterpret_cast<const void *>(k_eval_episodes<uint64_t, true>), nullptr},
+                                      {reinterpret_cast<const void *>(k_eval_episodes<uint32_t, true>), nullptr}}};
     if (!e || !net || !args) return fail(UAVENV_EINVAL, "null argument");
     const UavEvalArgs &u = *args;
     if (e->cfg.apf_enabled == 1) return fail(UAVENV_EINVAL, "uavenv_eval_episodes: APF envs are not supported");
     EVAL_TRY(eval_check_common(name, e, u, net->local));
-    EVAL_TRY(eval_check_dqn_net(name, -1, e, net, UAVENV_MFMA_F32));
+    EVAL_TRY(eval_check_dqn_net(name, -1, e, net, UAVENV_MFMA_F32, UAVENV_EVAL_MAX_OUTPUTS));
     HIP_TRY(hipSetDevice(e->cfg.device));
     StepArgs a = eval_step_args(e, u);
     EvalArgs v;
@@ -3362,7 +3436,7 @@ int uavenv_eval_episodes(UavEnv *e, const UavDqnNet *net, const UavEvalArgs *arg
     v.dueling = net->dueling;
     // (the wave slot: the work queue, then the wavefront's 64 packed rows)
     const size_t lds = eval_run_setup(e, u, v.run, uavq::kSplitF * 4, uavq::kMaxOut * uavq::kHid + uavq::kMaxOut, 64 * kPackedDwords * 4);
-    const void *fn = eval_kernel(e, kernels);
+    const void *fn = eval_kernel(e, v.n2 > 4 ? wide : kernels);    // (more than 4 outputs: layer 2 in groups of four)
     int grid = 0;
     EVAL_TRY(eval_grid(name, e, fn, lds, u.max_workgroups, 1, v.run, &grid));
     if (!e->eval_img) HIP_TRY(hipMalloc((void **)&e->eval_img, 2 * UAVENV_DQN_IMAGE_FLOATS * sizeof(float)));
@@ -3387,7 +3461,7 @@ int uavenv_eval_episodes_f16(UavEnv *e, const UavDqnNet *net, const UavEvalArgs 
     if (e->cfg.obs_dtype != UAVENV_OBS_F16 && e->cfg.obs_dtype != UAVENV_OBS_PACKED)
         return fail(UAVENV_EINVAL, "uavenv_eval_episodes_f16: needs an env with f16 or packed observation rows");
     EVAL_TRY(eval_check_common(name, e, u, net->local));
-    EVAL_TRY(eval_check_dqn_net(name, -1, e, net, UAVENV_MFMA_F16));
+    EVAL_TRY(eval_check_dqn_net(name, -1, e, net, UAVENV_MFMA_F16, 4));
     HIP_TRY(hipSetDevice(e->cfg.device));
     StepArgs a = eval_step_args(e, u);
     EvalArgs v;
@@ -3449,6 +3523,10 @@ int uavenv_eval_episodes_slots(UavEnv *e, const UavDqnNet *const *nets, int32_t 
                                           reinterpret_cast<const void *>(k_eval_episodes_slots<uint64_t, true>)},
                                          {reinterpret_cast<const void *>(k_eval_episodes_slots<uint32_t, false>),
                                           reinterpret_cast<const void *>(k_eval_episodes_slots<uint32_t, true>)}}};
+    static const EvalKernels wide = {{{reinterpret_cast<const void *>(k_eval_episodes_slots<uint64_t, false, true>),
+                                       reinterpret_cast<const void *>(k_eval_episodes_slots<uint64_t, true, true>)},
+                                      {reinterpret_cast<const void *>(k_eval_episodes_slots<uint32_t, false, true>),
+                                       reinterpret_cast<const void *>(k_eval_episodes_slots<uint32_t, true, true>)}}};
     if (!e || !nets || !args) return fail(UAVENV_EINVAL, "null argument");
     const UavEvalArgs &u = *args;
     EVAL_TRY(eval_check_common(name, e, u, nullptr));
@@ -3458,7 +3536,7 @@ int uavenv_eval_episodes_slots(UavEnv *e, const UavDqnNet *const *nets, int32_t 
     for (int k = 0; k < n_nets; ++k) {
         const UavDqnNet *net = nets[k];
         if (!net) return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: net %d is NULL", k);
-        EVAL_TRY(eval_check_dqn_net(name, k, e, net, UAVENV_MFMA_F32));
+        EVAL_TRY(eval_check_dqn_net(name, k, e, net, UAVENV_MFMA_F32, UAVENV_EVAL_MAX_OUTPUTS));
         if ((net->dueling ? 1 : 0) != (nets[0]->dueling ? 1 : 0))
             return fail(UAVENV_EINVAL, "uavenv_eval_episodes_slots: net %d differs from net 0 in dueling", k);
         if (((uintptr_t)net->local) & 15u)
@@ -3476,7 +3554,7 @@ int uavenv_eval_episodes_slots(UavEnv *e, const UavDqnNet *const *nets, int32_t 
     v.dueling = nets[0]->dueling;
     // (the wave slot: the work queue, then the wavefront's 64 packed rows)
     const size_t lds = eval_run_setup(e, u, v.run, uavq::kSplitF * 4, uavq::kMaxOut * uavq::kHid + uavq::kMaxOut, 64 * kPackedDwords * 4);
-    const void *fn = eval_kernel(e, kernels);
+    const void *fn = eval_kernel(e, v.n2 > 4 ? wide : kernels);    // (more than 4 outputs: layer 2 in groups of four)
     int grid = 0;
     EVAL_TRY(eval_grid(name, e, fn, lds, u.max_workgroups, n_nets, v.run, &grid));
     // the nets' layer-1 images, two per image call (nets 2k and 2k + 1; the last net twice when n_nets is odd), in a buffer of this

@@ -134,6 +134,9 @@ def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int
     (an APF env keeps one [K, 3] f64 sub-goal list per resident lane, 256 lanes per workgroup).  A single learner with
     mfma = "f16" goes through uavenv_eval_episodes_f16 -- the f16-MFMA forward it acts with, on the halves an f16 or packed env
     feeds it -- and needs a non-APF env with f16 or packed rows; the list and APF forms take f32-MFMA learners only.
+    Heads: f32-MFMA learners of up to _lib.EVAL_MAX_OUTPUTS = 14 layer-2 outputs (n_actions + 1 for a dueling net) -- above 4 the
+    same entries launch the kernels' wide instantiation, with the same Q values bit for bit as the learner's act launch -- and
+    f16-MFMA learners of up to 4; ValueError beyond, before anything is enqueued.
 
     scenarios: None (the env's bank) or (start_goal [m,6] f64, sub_goals [m,K,3] f64, n_sub [m] i32) device tensors, e.g.
     held_out_scenarios(env, m, seed).  v0: [n,2] raw initial V_vector per episode (default: headings from Philox(seed, e)).
@@ -156,6 +159,11 @@ def evaluate_policy(env, learner, n_episodes: int, *, scenarios=None, first: int
         if any(getattr(L, "mfma", "f32") != "f32" for L in ls):
             raise ValueError("the per-slot form (a list of learners) takes f32-MFMA nets only; evaluate an f16-MFMA learner on its own")
     f16 = not as_list and getattr(learner, "mfma", "f32") == "f16"
+    n2 = max(int(getattr(L.net, "n_actions", 0)) + (1 if getattr(L.net, "dueling", 0) else 0) for L in ls)
+    if n2 > _lib.EVAL_MAX_OUTPUTS:
+        raise ValueError(f"the episode kernels take heads of at most {_lib.EVAL_MAX_OUTPUTS} layer-2 outputs (n_actions + dueling; got {n2})")
+    if f16 and n2 > 4:
+        raise ValueError(f"an f16-MFMA learner is evaluated with at most 4 layer-2 outputs (n_actions + dueling; got {n2})")
     if v0 is not None and tuple(np.shape(v0)) != (n, 2):
         raise ValueError(f"v0 must be [{n}, 2] (got {tuple(np.shape(v0))})")
     if as_list and len(ls) != 1 and len(ls) != env.uav_per_env:

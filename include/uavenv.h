@@ -497,9 +497,13 @@ int uavenv_dqn_reduce_adam_slots(const UavDqnNet *const *nets, int32_t n_nets, f
  * The call never reads or writes the env's agents, its tick, a pending uavenv_set_step_meta or the moved word: a training run is
  * the same with or without evaluations between its calls.  Calls on one env run in stream order (they share the env's layer-1
  * image scratch).  Takes non-APF envs with a world, f32-MFMA nets of the uavenv_step_policy shape (w 100, hid 64, the env's
- * n_actions >= 2, at most 4 layer-2 outputs); UAVENV_EINVAL otherwise, and for n <= 0, first < 0, misaligned pointers (16 bytes:
- * net->local, records), caller scenarios with m <= 0 or only some of the three pointers, no scenarios at all, traj_steps > 0
- * without both trajectory pointers (or >= 2^30), or n so large that n + the grid's lanes exceeds INT32_MAX. */
+ * n_actions >= 2, at most UAVENV_EVAL_MAX_OUTPUTS layer-2 outputs); UAVENV_EINVAL otherwise, and for n <= 0, first < 0, misaligned
+ * pointers (16 bytes: net->local, records), caller scenarios with m <= 0 or only some of the three pointers, no scenarios at all,
+ * traj_steps > 0 without both trajectory pointers (or >= 2^30), or n so large that n + the grid's lanes exceeds INT32_MAX.
+ * Heads of more than 4 layer-2 outputs (n_actions + dueling: finer steering tables, a dueling net of 4 actions) run a second
+ * instantiation of the same kernel whose layer 2 goes in groups of four outputs; every Q value, the dueling combination and the
+ * first maximum are still bit for bit those of uavenv_dqn_act.  The narrower heads launch what they always launched. */
+#define UAVENV_EVAL_MAX_OUTPUTS 14  /* layer-2 outputs uavenv_eval_episodes / _slots take: what uavenv_dqn_act / uavenv_dqn_grad take */
 #define UAVENV_EVAL_SUCCESS 1       /* the agent reached the goal (or had no sub-goal left) */
 #define UAVENV_EVAL_LOSE 2          /* Step reached Max_Step */
 #define UAVENV_EVAL_TRUNCATED 4     /* stopped by max_steps (or the natural bound) before the agent was done */
@@ -558,8 +562,8 @@ int uavenv_eval_episodes_f16(UavEnv *env, const UavDqnNet *net, const UavEvalArg
  * lists, agents, tick, pending uavenv_set_step_meta and moved word are never touched.  max_workgroups bounds the workgroups PER NET.
  * The nets' layer-1 images live in a buffer of this entry's own on the env (allocated on first use, grown when n_nets needs it).
  * Calls on one env run in stream order.  A record does not depend on the grid.
- * Takes f32-MFMA nets of w 100, hid 64, the env's n_actions >= 2 and at most 4 layer-2 outputs, all with the same `dueling`, each
- * with a 16-byte aligned `local`.  UAVENV_EINVAL, with nothing enqueued or allocated, otherwise and for: no world; nets NULL or a NULL
+ * Takes f32-MFMA nets of w 100, hid 64, the env's n_actions >= 2 and at most UAVENV_EVAL_MAX_OUTPUTS layer-2 outputs, all with the same
+ * `dueling`, each with a 16-byte aligned `local` (wide heads: as uavenv_eval_episodes). UAVENV_EINVAL, with nothing enqueued or allocated, otherwise and for: no world; nets NULL or a NULL
  * entry; n_nets other than 1 or uav_per_env (or > UAVENV_SAC_LOOP_MAX_SLOTS); and every argument uavenv_eval_episodes refuses. */
 int uavenv_eval_episodes_slots(UavEnv *env, const UavDqnNet *const *nets, int32_t n_nets, const UavEvalArgs *args, void *stream);
 

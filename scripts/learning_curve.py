@@ -6,6 +6,9 @@ The settings (envs, learner batch, replay capacity, trainer, training epsilon, r
 uniform random policy) and the scripted baseline (sub-goal pursuit among the same three actions, no learning:
 uavenv_eval_episodes_scripted) with look-ahead 0 and 8.  Held-out rows are planned on a seed the training bank never uses.  Output: one JSON document.
     python scripts/learning_curve.py [--passes 1000000] [--every 50000] [--episodes 16384] [--out profiles/learning_curve_configs1.json]
+--actions N (configs[1] only; default 3, bench.py's): the same run with a steering table of N actions, 2 <= N + (1 for a dueling
+trainer) <= 14 -- above 4 layer-2 outputs the evaluations go through the wide instantiation of the episode kernel; the scripted baseline
+chooses among the same N actions.  Output: profiles/learning_curve_configs1_aN.json.
 
 --config 2: BASELINE configs[2] as `bench.py --config 3` builds it (65 536 envs, dueling + DDQN, f16 observation rows, the f16-MFMA
 learner, HotLoop), evaluated through uavenv_eval_episodes_f16: the f16 policy the learner acts with, on the halves the f16 ring
@@ -197,12 +200,15 @@ def main():
     ap.add_argument("--episodes", type=int, default=None)
     ap.add_argument("--max-steps", type=int, default=0, help="evaluation truncation (0: natural episode ends)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--actions", type=int, default=3, help="--config 1: the size of the steering table (default 3: bench.py's run)")
     args = ap.parse_args()
+    if args.actions != 3 and args.config != 1:
+        raise SystemExit("--actions goes with --config 1 (the f16-MFMA learner of configs[2] takes at most 4 outputs, configs[3] is SAC)")
     c3 = args.config == 3
     args.passes = args.passes if args.passes is not None else (40000 if c3 else 1000000)
     args.every = args.every if args.every is not None else (4000 if c3 else 50000)
     args.episodes = args.episodes if args.episodes is not None else (4096 if c3 else 16384)
-    args.out = args.out or "profiles/learning_curve_configs%d.json" % args.config
+    args.out = args.out or "profiles/learning_curve_configs%d%s.json" % (args.config, "" if args.actions == 3 else "_a%d" % args.actions)
     if c3:
         return main_config3(args)
     c2 = args.config == 2
@@ -211,23 +217,26 @@ def main():
         raise SystemExit("bench.py --config 3 is expected to be the dueling f16-MFMA learner on f16 rows")
     if not c2 and (b.trainer not in ("dqn", "ddqn", "dueling") or b.mfma != "f32"):
         raise SystemExit("bench.py's default run is expected to be the f32 DQN family")
+    A = args.actions
+    if A < 2 or A + (1 if b.trainer == "dueling" else 0) > 14:
+        raise SystemExit("--actions: 2 <= N, and N (+ 1 for a dueling trainer) <= 14 layer-2 outputs")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     bank_size = b.bank_size or max(b.envs, 4096)            # (bench.py run_dqn: the bank without rolling refresh)
     env = make_city26_env(b.envs, bank=b.bank, bank_size=bank_size, bank_seed=42, device=dev,
-                          obs_dtype=torch.float16 if c2 else "packed")
+                          obs_dtype=torch.float16 if c2 else "packed", n_actions=A)
     ring = DeviceReplayRing(env, b.replay, discrete=True)
     ring.reset(seed=1000)
     torch.manual_seed(42)
     net = "VAnet2" if b.trainer == "dueling" else "Qnet2"
-    learner = FusedDQNLearner({"NetWork": net, "w": "100", "hiden_dim": "64", "output": "3"}, b.trainer, device=dev, mfma=b.mfma)
+    learner = FusedDQNLearner({"NetWork": net, "w": "100", "hiden_dim": "64", "output": str(A)}, b.trainer, device=dev, mfma=b.mfma)
     loop = HotLoop(ring, learner, b.batch, 7, eps=b.eps)
     scn = ev.held_out_scenarios(env, args.episodes, seed=HELD_OUT_SEED)
     what = ("configs[2] training (bench.py --config 3: dueling DDQN, f16 rows, f16 MFMA) with greedy held-out evaluations of the "
             "f16 policy (uavenv_eval_episodes_f16)") if c2 else "configs[1] training (bench.py defaults) with greedy held-out evaluations"
     out = {"what": what, "settings": {
                "envs": b.envs, "batch": b.batch, "replay": b.replay, "trainer": b.trainer, "mfma": b.mfma, "obs_dtype": b.obs_dtype,
-               "train_eps": b.eps, "bank": b.bank,
+               "train_eps": b.eps, "bank": b.bank, "n_actions": A,
                "bank_size": bank_size, "passes": args.passes, "every": args.every, "eval_episodes": args.episodes,
                "eval_max_steps": args.max_steps, "held_out_seed": HELD_OUT_SEED},
            "baselines": {"untrained_greedy": evaluation(env, learner, scn, args.episodes, args.max_steps),

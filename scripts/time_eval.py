@@ -36,6 +36,13 @@ default form (k_apf_adjust + k_step on the APF env).  Launches only, device even
 alternating in the same process, median of the repeats; every record checked equal before a time is taken.  --once N: no timing, one
 launch per APF setting at N episodes (for a kernel-trace run).
     python scripts/time_eval.py --scripted [--reps 5] [--max-steps 600] [--lookahead 8] [--out profiles/eval_scripted_times.json]
+
+--wide: heads of more than 4 layer-2 outputs (a 9-action Qnet2; a 13-action dueling VAnet2 = 14 outputs) through the wide
+instantiations of k_eval_episodes / k_eval_episodes_slots: one net on a non-APF env, four nets (U = 4) with APF off and on, each against
+set_state + per step one uavenv_dqn_act per net (eps = -1; four nets: slot rows gathered, actions scattered) + uavenv_step with
+SKIP_DONE.  Launches only, device events, a warm-up of both forms, then the two forms alternating in the same process, median of the
+repeats; every record checked equal before a time is taken.
+    python scripts/time_eval.py --wide [--reps 5] [--max-steps 600] [--out profiles/eval_wide_times.json]
 """
 from __future__ import annotations
 
@@ -670,6 +677,107 @@ def main_slots_once(args):
         env.close()
 
 
+class WideComposition(SlotsComposition):
+    """SlotsComposition on an env of A actions (nets of more than 4 layer-2 outputs); U = len(Ls) may be 1."""
+
+    def __init__(self, Ls, scn, n, v0, apf, max_steps, A):
+        U = len(Ls)
+        self.Ls, self.n, self.U, self.max_steps = Ls, n, U, max_steps
+        sg, sub, ns = (x.cpu().numpy() for x in scn)
+        rows = np.arange(n) % len(sg)
+        self.env = make_city26_env(n // U, obs_dtype="packed", uav_per_env=U, apf_enabled=apf, n_actions=A)
+        if apf:
+            self.env.set_buildings(self.env.buildings, velocities=apf_velocities(len(self.env.buildings)))
+        self.kin = np.concatenate([sg[rows, :3], v0, sg[rows, 3:]], 1)
+        self.nsub = ns[rows]
+        self.sub = sub[rows]
+        d = self.env.device
+        self.obs = [self.env.new_obs(), self.env.new_obs()]
+        self.act = torch.zeros(n, dtype=torch.int32, device=d)
+        self.rows_j = torch.zeros((n // U, self.obs[0].shape[1]), dtype=self.obs[0].dtype, device=d)
+        self.act_j = torch.zeros(n // U, dtype=torch.int32, device=d)
+        self.r64 = torch.zeros(n, dtype=torch.float64, device=d)
+        self.en = torch.zeros(n, dtype=torch.float64, device=d)
+        self.info = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.adone = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.valid = torch.zeros(n, dtype=torch.uint8, device=d)
+
+    def step(self, t):
+        if self.U > 1:
+            return SlotsComposition.step(self, t)
+        e, o0, o1 = self.env, self.obs[t % 2], self.obs[(t + 1) % 2]
+        self.Ls[0].act(o0, -1.0, 5, t, index_out=self.act)           # (one net: no gather, no scatter)
+        _lib.check(e.lib.uavenv_step(e._h, self.act.data_ptr(), _lib.ACT_INDEX_I32, o1.data_ptr(), self.r64.data_ptr(), None,
+                                     None, self.adone.data_ptr(), self.info.data_ptr(), self.valid.data_ptr(),
+                                     self.en.data_ptr(), None, _lib.STEP_SKIP_DONE, e._stream()), "uavenv_step")
+
+
+def main_wide(args):
+    """Heads of more than 4 layer-2 outputs (the wide instantiations of k_eval_episodes / k_eval_episodes_slots): a 9-action Qnet2
+    and a 13-action dueling VAnet2 (14 outputs), untrained; one net on a non-APF env, and four nets (U = 4) with APF off and on;
+    each against the composed launches that take such heads: set_state + per step uavenv_dqn_act per net (eps = -1) + uavenv_step."""
+    torch.cuda.set_device(0)
+    probe = make_city26_env(64, obs_dtype="packed")
+    scn = ev.held_out_scenarios(probe, 16384, seed=0xE7A1)
+    probe.close()
+    out = {"what": "greedy evaluation of untrained wide heads (Qnet2 with 9 actions; dueling VAnet2 with 13 actions = 14 layer-2 "
+                   "outputs) in one launch on held-out city26 episodes against set_state + per step uavenv_dqn_act per net (eps = -1; "
+                   "four nets: slot rows gathered, actions scattered) + uavenv_step (k_apf_adjust + k_step with APF on).  Launches only, "
+                   "device events, a warm-up, the two forms alternating, median of %d" % args.reps,
+           "max_steps": args.max_steps, "sizes": []}
+    for net, kind, A in (("Qnet2", "dqn", 9), ("VAnet2", "dueling", 13)):
+        for U, apf in ((1, 0), (4, 0), (4, 1)):
+            Ls = []
+            for j in range(U):
+                torch.manual_seed(j)
+                Ls.append(FusedDQNLearner(dict(PARAM, NetWork=net, output=str(A)), kind, device="cuda:0"))
+            for n in (int(x) for x in args.sizes.split(",")):
+                v0 = np.random.default_rng(n).uniform(0, 2 * np.pi, n)
+                v0 = np.stack([np.cos(v0), np.sin(v0)], 1)
+                comp = WideComposition(Ls, scn, n, v0, apf, args.max_steps, A)
+                ref, n_steps = comp.records()
+                kw = dict(scenarios=scn, v0=v0, max_steps=args.max_steps)
+                who = Ls if U > 1 else Ls[0]
+                res = ev.evaluate_policy(comp.env, who, n, **kw)
+                rec = res.host_records()
+                ok = (np.array_equal(rec["ret"], ref["ret"]) and np.array_equal(rec["energy"], ref["energy"]) and
+                      np.array_equal(rec["steps"], ref["steps"]) and np.array_equal(rec["outcome"], ref["outcome"]))
+                if not ok:
+                    raise SystemExit(f"{net} A = {A}, U = {U}, apf {apf}, n = {n}: the kernel's records differ from the composition's; "
+                                     "no time reported")
+                agent_steps = int(rec["steps"].sum())
+
+                def timed_eval():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    a.record()
+                    ev.evaluate_policy(comp.env, who, n, **kw)
+                    b.record()
+                    b.synchronize()
+                    return a.elapsed_time(b)
+
+                timed_eval()
+                comp.timed(min(n_steps, 32))
+                t_eval, t_comp = [], []
+                for _ in range(args.reps):               # the two forms alternating
+                    t_eval.append(timed_eval())
+                    t_comp.append(comp.timed(n_steps))
+                me, mc = float(np.median(t_eval)), float(np.median(t_comp))
+                row = {"net": net, "n_actions": A, "outputs": A + (kind == "dueling"), "nets": U, "apf": apf, "episodes": n,
+                       "agent_steps": agent_steps, "steps_longest": n_steps, "records_equal": True,
+                       "eval_ms": me, "eval_ms_all": t_eval, "comp_ms": mc, "comp_ms_all": t_comp,
+                       "comp_form": ("4 x (gather + dqn_act + scatter)" if U > 1 else "dqn_act") + (" + apf_adjust + step" if apf else " + step"),
+                       "eval_agent_steps_per_s": agent_steps / (me * 1e-3), "comp_agent_steps_per_s": agent_steps / (mc * 1e-3),
+                       "eval_us_per_episode": me * 1e3 / n, "comp_us_per_episode": mc * 1e3 / n, "speedup": mc / me,
+                       "summary": res.summary()}
+                print(json.dumps({k: v for k, v in row.items() if not k.endswith("_all") and k != "summary"}), flush=True)
+                out["sizes"].append(row)
+                comp.env.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="16384,65536,262144")
@@ -682,7 +790,11 @@ def main():
     ap.add_argument("--once", type=int, default=0, help="--slots / --scripted: no timing, one launch per APF setting at this many episodes (per net)")
     ap.add_argument("--scripted", action="store_true", help="time uavenv_eval_episodes_scripted (the scripted baseline, APF off and on) instead")
     ap.add_argument("--lookahead", type=int, default=8, help="--scripted: the policy's look-ahead")
+    ap.add_argument("--wide", action="store_true", help="time the wide heads (9-action Qnet2, 13-action VAnet2: one net, four nets, APF off and on) instead")
     args = ap.parse_args()
+    if args.wide:
+        args.out = args.out or "profiles/eval_wide_times.json"
+        return main_wide(args)
     if args.scripted:
         args.out = args.out or "profiles/eval_scripted_times.json"
         return main_scripted(args)
